@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- SOT-loss evaluations/s on [B, N_fft] spectrum pairs (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: the contract fields, `config` and the headline kernel's
+`roofline` (measured inside the timed region).  --full adds everything that takes runs of its own: the roofline side kernels
+(paper mode, merge pipeline, training form), the two-stream and stream-event timings, the secondary workloads under `extras`
+(unless --no-extras), the CPU baseline (unless --no-cpu-baseline) and the parity check against the stored reference scalar.
+--dump-outputs DIR writes what the last timed step returned (DIR/loss.npy, DIR/row_losses.npy) for output-for-output comparisons.
 
 N = 1 runs in this process.  N > 1: when the process is not already a rank (no RANK in the environment) it starts N fresh
 rank processes -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py ...` as a
@@ -18,7 +24,7 @@ cannot serve them.
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline     -- dominant kernel (sot_forward_full_kernel: the forward specialised for rows that fill their geometry): algorithmic bytes per launch / average launch
                   duration measured live with HIP events attached to its dispatches inside the timed region;
-  cpu_baseline -- the op-for-op torch restatement of the reference (oracle/torch_restatement.py,
+  cpu_baseline -- (--full) the op-for-op torch restatement of the reference (oracle/torch_restatement.py,
                   kind "port") timed on this host's cores on a bounded sample of the same workload.
 """
 from __future__ import annotations
@@ -61,7 +67,12 @@ def parse():
                          "overlaps the next step's forward kernel; 0 (default) = 1 on one GPU (per-kernel times then agree "
                          "with rocprofv3), 2 when there is a collective to hide (N > 1)")
     ap.add_argument("--cpu-rows", type=int, default=8192)   # all rows of the headline workload (set 0); ~15 s of CPU work
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary workloads reported under `extras`")
+    ap.add_argument("--no-extras", action="store_true", help="skip the secondary workloads reported under `extras` (with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline side kernels, two-stream / stream-event timings, the "
+                         "secondary workloads, the CPU baseline and the parity check (off: only the headline figure)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, row losses) as DIR/<name>.npy")
     ap.add_argument("--global-rows", type=int, default=0,
                     help="STRONG scaling (BASELINE config 3: 65536): the total batch is fixed and every rank takes global / N rows "
                          "(shard r = the rows [r, r + 1) * global / N of the 8 x 8192-row blocks seeded 1234 + block); overrides --rows")
@@ -736,7 +747,7 @@ def rccl_world1_probe():
         for k in list(env):   # a profiler around this bench (rocprofv3 preloads its tool library) must not follow into the child tree
             if k == "LD_PRELOAD" or k.startswith(("ROCP_", "ROCPROF", "ROCPROFILER_", "HSA_TOOLS_")):
                 env.pop(k)
-        cmd = launcher_command(1, ["--gpus", "1", "--steps", "200", "--warmup", "20", "--prewarm", "200", "--no-extras", "--no-cpu-baseline"], port)
+        cmd = launcher_command(1, ["--gpus", "1", "--steps", "200", "--warmup", "20", "--prewarm", "200", "--full", "--no-extras", "--no-cpu-baseline"], port)
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         if r.returncode != 0 or not line:
@@ -853,6 +864,23 @@ def flatten_for_scalar_readers(rec, B, N):
         cb["paper_mode_scalar"] = pm.get("scalar")
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 / float64.  When the arrays together exceed `limit`, every 1-D
+    array larger than its share is cut to a fixed, seeded sample of its elements (the same indices in every run of the same shape)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.array(v, dtype=np.float64 if v.dtype == np.float64 else np.float32, order="C") for k, v in arrays.items()}   # 0-d stays 0-d
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > limit and a.ndim == 1 and a.nbytes > limit // len(arrays):
+            keep = (limit // len(arrays)) // a.itemsize
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def event_stride(steps):
     # never more than every 4th step: a timed dispatch is preceded / followed by its event packets (+ ~8 us when EVERY step is timed)
     return int(os.environ.get("SOT_BENCH_EVENT_STRIDE", str(max(4, -(-steps // PROFILE_SLOTS)))))
@@ -862,6 +890,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
     # stdout carries exactly ONE line (rank 0's JSON): native libraries print there too (RCCL's version banner at
@@ -1024,14 +1054,21 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt)
     del out
+    if args.dump_outputs and rank == 0:
+        # the buffers the last timed step wrote (slot of step K - 1; a replayed graph holds the slot of the step it captured), copied
+        # before anything else reuses them
+        last = args.steps - 1
+        slot = (last % len(graphs) if graphs is not None else last) % len(ring)
+        dump = {"loss": (ring[slot] * inv_global_rows) if dist_on else meanbuf[slot], "row_losses": rowbuf[slot]}
+        write_outputs(args.dump_outputs, {k: v.detach().cpu().numpy() for k, v in dump.items()})
     leave_lanes()  # back to the default stream for the secondary measurements
 
-    if graphs is not None:  # a replay carries no kernel-attached events: time the dominant kernel eagerly after the timed region
+    if graphs is not None and args.full:  # a replay carries no kernel-attached events: time the dominant kernel eagerly after the timed region
         timed_slots = list(range(min(args.steps, 50)))
         for i in timed_slots:
             step(i, i)
         torch.cuda.synchronize()
-    kern_ms = sum(nat.profile_elapsed_ms(sl) for sl in timed_slots) / len(timed_slots)
+    kern_ms = sum(nat.profile_elapsed_ms(sl) for sl in timed_slots) / len(timed_slots) if timed_slots else None
 
     def attached_ms(call, count=32):
         """Average duration of the FIRST kernel `call(i)` launches (a compile-time-length row kernel), from HIP events attached to
@@ -1048,7 +1085,7 @@ def main():
     # The pipeline north_star names (merge of the two CDFs = sort + searchsorted) on the SAME workload, in the paper's mode, and the
     # training form (loss + d/dy in one pass): kernel-attached times and their roofline fractions next to the headline kernel's.
     side = {}
-    if not dist_on and FULL_ROW_GEOMETRY.get(N) is not None:
+    if args.full and not dist_on and FULL_ROW_GEOMETRY.get(N) is not None:
         cutm = Wasserstein1D(**MODES["cutoff"]).to(dev)
         cm = [cutm._marshal(x, y, pos_x, pos_y, {}) for x, y in sets]
 
@@ -1102,7 +1139,7 @@ def main():
 
     extras = {"host_enqueue_ms_per_step": 1e3 * host_enqueue / args.steps, "kernel_timing": f"kernel-attached HIP events on {len(timed_slots)} "
               f"launches of the timed region (every {EVENT_STRIDE}th step)"}
-    if not dist_on and n_lanes == 1 and not graph_mode:
+    if args.full and not dist_on and n_lanes == 1 and not graph_mode:
         # the same steps pipelined over two HIP streams (what --lanes 2 times, and what N > 1 does to hide the collective): a step's
         # launch gap, pipeline fill / drain and mean kernel then overlap its neighbour's row kernel.  Not the default on one GPU:
         # overlapped kernels share the chip, so their individual durations (kernel_ms, rocprofv3) stop describing the kernel.
@@ -1119,36 +1156,37 @@ def main():
         torch.cuda.synchronize()
         extras["two_streams_ms_per_step"] = 1e3 * (time.perf_counter() - t2) / k2
         extras["two_streams_rows_per_s"] = B / (extras["two_streams_ms_per_step"] * 1e-3)
-    with torch.no_grad():   # the same kernel between two events recorded on the stream around the call (round 1's method)
-        x2, y2, xp, yp, flags, plan, _ = marshalled[0]
-        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
-        for k, (ea, eb) in enumerate(pairs):
-            x2, y2, xp, yp, flags, plan, _ = marshalled[k % len(marshalled)]
-            ea.record()
-            nat.forward_rows(x2, y2, xp, yp, float(mod.p), flags, plan, rowbuf[0])
-            eb.record()
-            nat.reduce_mean(rowbuf[0])
-        torch.cuda.synchronize()
-        extras["kernel_ms_between_stream_events"] = sum(ea.elapsed_time(eb) for ea, eb in pairs) / len(pairs)
+    if args.full:
+        with torch.no_grad():   # the same kernel between two events recorded on the stream around the call (round 1's method)
+            x2, y2, xp, yp, flags, plan, _ = marshalled[0]
+            pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+            for k, (ea, eb) in enumerate(pairs):
+                x2, y2, xp, yp, flags, plan, _ = marshalled[k % len(marshalled)]
+                ea.record()
+                nat.forward_rows(x2, y2, xp, yp, float(mod.p), flags, plan, rowbuf[0])
+                eb.record()
+                nat.reduce_mean(rowbuf[0])
+            torch.cuda.synchronize()
+            extras["kernel_ms_between_stream_events"] = sum(ea.elapsed_time(eb) for ea, eb in pairs) / len(pairs)
     n_extra = max(10, min(args.steps, 50))
-    if dist_on:  # BASELINE config 3: report the step with and without the collective
+    if args.full and dist_on:  # BASELINE config 3: report the step with and without the collective
         def local_only(i):
             with torch.no_grad():
                 x2, y2, xp, yp, flags, plan, _ = marshalled[i % len(sets)]
                 nat.reduce_mean(nat.forward_rows(x2, y2, xp, yp, float(mod.p), flags, plan, rowbuf[i % 4]), sum_out=ring[i % len(ring)])
         extras["ms_per_step_without_collective"] = timed(local_only, n_extra)
-    elif not args.no_extras:
+    elif args.full and not args.no_extras:
         del sets[4:], marshalled[4:]   # four rotating sets (512 MiB) still exceed the Infinity Cache
         extras.update(other_workloads(dev, nat, sets, pos_x, pos_y, timed, n_extra))
         extras.update(paper_loss_workloads(dev, nat, timed, n_extra))
     bytes_per_row = 4 * (N + N) + 4  # fwd, shared positions
-    achieved = bytes_per_row * B / (kern_ms * 1e-3) / 1e9
+    achieved = bytes_per_row * B / (kern_ms * 1e-3) / 1e9 if kern_ms else None
 
     if rank == 0:
         parity = None
         try:
             man = json.load(open(os.path.join(ROOT, "tests", "golden", "manifest.json")))
-            if (B, N) == (8192, 2048) and world == 1:  # the stored scalar is that of seed 1234 alone
+            if args.full and (B, N) == (8192, 2048) and world == 1:  # the stored scalar is that of seed 1234 alone
                 want = man["_config2_b8192n2048_seed1234"][f"uniform_{args.mode}"]
                 parity = abs(first - want) / abs(want)
         except Exception:
@@ -1188,7 +1226,7 @@ def main():
                        "collective": "none" if not dist_on else "one RCCL all-reduce(SUM) of the fp64 partial sum per step" + (" (HIP-graph replay)" if args.graph_steps else ""),
                        "parity_rel_err_vs_reference_scalar": parity, "loss_set0": first, **rccl_seen},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                         "frac": achieved / HBM_PEAK_GBS if achieved is not None else None, "traffic": traffic, "traffic_source": traffic_source,
                          "kernel": forward_kernel_name(N, args.mode, batch=B), "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": bytes_per_row * B,
                          "headline_is": ("merge-free p=1 kernel (both measures on one sorted grid: no sort, no search, no merge); the merge pipeline "
                                          "north_star describes: see roofline.merge_p1 / roofline.paper_mode / roofline.training_form")
@@ -1196,7 +1234,7 @@ def main():
                          **side},
             "extras": extras,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.mode, N, min(args.cpu_rows, B), 1234)
         flatten_for_scalar_readers(rec, B, N)
         sys.stdout.flush()

@@ -1,7 +1,10 @@
-"""bench.py --gpus N: the rank launcher (CPU; no GPU is touched).  BASELINE config 3 / SURVEY 8(e): one process per GPU."""
+"""bench.py --gpus N: the rank launcher (CPU; no GPU is touched).  BASELINE config 3 / SURVEY 8(e): one process per GPU.  Also the
+plain / --full split and --dump-outputs (one -m gpu test runs a plain line)."""
 import os
 import subprocess
 import sys
+
+import pytest
 
 from conftest import ROOT
 
@@ -137,3 +140,63 @@ def test_the_line_says_what_rccl_saw():
     src = open(BENCH).read()
     assert "rccl_world_size" in src and "rccl_allreduce_ones" in src and "dist.all_reduce(ones)" in src
     assert src.index("dist.all_reduce(ones)") < src.index("def native_step")    # before anything is timed
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """--full (off by default) carries everything beyond the headline figure; --dump-outputs DIR is off by default."""
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    ns = b.parse()
+    assert ns.full is False and ns.dump_outputs is None and ns.steps == 7 and ns.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    ns = b.parse()
+    assert ns.full is True and ns.dump_outputs == "out"
+    src = open(BENCH).read()
+    for guarded in ("if args.full and world == 1 and not args.no_cpu_baseline", "elif args.full and not args.no_extras",
+                    "if args.full and not dist_on and FULL_ROW_GEOMETRY.get(N) is not None"):
+        assert guarded in src
+
+
+def test_write_outputs_keeps_float_dtypes_and_samples_within_the_limit(tmp_path):
+    import numpy as np
+    b = _bench_module()
+    rows = np.arange(1000, dtype=np.float32)
+    b.write_outputs(str(tmp_path / "a"), {"loss": np.array(2.5, np.float32), "row_losses": rows, "sum": np.array(3.0)})
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and float(loss) == 2.5
+    assert np.array_equal(np.load(tmp_path / "a" / "row_losses.npy"), rows)
+    assert np.load(tmp_path / "a" / "sum.npy").dtype == np.float64
+    # over the limit: a fixed, seeded sample of the large array, the same in every run
+    b.write_outputs(str(tmp_path / "b"), {"loss": np.float32(1.0), "row_losses": rows}, limit=800)
+    b.write_outputs(str(tmp_path / "c"), {"loss": np.float32(1.0), "row_losses": rows}, limit=800)
+    s1, s2 = np.load(tmp_path / "b" / "row_losses.npy"), np.load(tmp_path / "c" / "row_losses.npy")
+    assert s1.nbytes <= 400 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs_match_the_oracle(tmp_path):
+    """A plain run prints the contract fields and, with --dump-outputs, the last timed step's loss and row losses.  With 7 steps over 6
+    rotating sets the last step reads set 0 (seed 1234, drawn on the CPU): its rows are checked against the C oracle."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "7", "--warmup", "2", "--prewarm", "10", "--rows", "512",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "sot_loss_evals_per_sec" and rec["unit"] == "rows/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["steps"] == 7 and rec["ms_per_step"] > 0 and abs(rec["value"] - 512 * 1e3 / rec["ms_per_step"]) <= 1e-6 * rec["value"]
+    assert "cpu_baseline" not in rec and "paper_mode" not in rec["roofline"]     # --full only
+    loss, rows = np.load(out / "loss.npy"), np.load(out / "row_losses.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and rows.dtype == np.float32 and rows.shape == (512,)
+    from oracle import sot_oracle as so
+    from sot_amd.bench_inputs import spectrum_pairs
+    x, y = spectrum_pairs("uniform", 512, 2048, 2048, 1234)
+    import torch
+    lin = torch.linspace(0, 1, 2048).numpy()
+    want = so.forward(x.numpy(), y.numpy(), lin, lin.copy(), p=1.0, flags=so.make_flags(False, False, False, True))
+    assert np.allclose(rows, want, rtol=1e-5, atol=1e-6 * float(np.abs(want).max()))
+    assert abs(float(loss) - float(so.mean(want))) <= 1e-5 * abs(float(so.mean(want)))

@@ -50,7 +50,7 @@ def test_bench_rank_process_runs_the_collective_branch():
     """bench.py as the driver launches it for N > 1 (a rank of torch.distributed.run), with SOT_BENCH_FORCE_DIST=1 so that ONE
     rank takes the RCCL branch: two alternating streams, one all-reduce(SUM) of the fp64 partial sum per step."""
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5", "--prewarm", "40", "--rows", "2048",
-                   "--no-extras", "--no-cpu-baseline"], {"SOT_BENCH_FORCE_DIST": "1"})
+                   "--full", "--no-extras", "--no-cpu-baseline"], {"SOT_BENCH_FORCE_DIST": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]          # exactly one JSON line on stdout (RCCL's banner goes to stderr)

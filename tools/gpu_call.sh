@@ -35,7 +35,7 @@ case "$CASE" in
   bench)                # <tag> [bench args]: the bench line
     O="gpurun_out/${1:-r5}"; shift || true
     mkdir -p "$O"
-    timeout 1500 python bench.py "$@" > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
+    timeout 1500 python bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
     tail -n 3 "$O/bench.err"
     python3 - "$O/bench.json" <<'PY'
 import json, sys

@@ -7,10 +7,10 @@ case " $* " in *" --gpus "*) echo "profile_round.sh profiles ONE process: bench.
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 30 --warmup 5 --no-cpu-baseline --no-extras $*"
+ARGS="--steps 30 --warmup 5 --full --no-cpu-baseline --no-extras $*"
 # kernel-trace stats of the WHOLE bench command (extras included: per-row positions, segmented sort, position gradients, the paper's loss
 # step and MSSLoss, config 5 ...), then of the headline-only command the PMC passes below use (its steady-state averages)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_extras -- python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline $* > $OUT/stats_extras.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_extras -- python3 bench.py --steps 30 --warmup 5 --full --no-cpu-baseline $* > $OUT/stats_extras.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py $ARGS > $OUT/stats.log 2>&1
 pass() { # name, counters...
   local name=$1; shift
