@@ -50,9 +50,6 @@ __device__ __forceinline__ MassPlan make_mass_plan(int n)
 template <bool SQ>
 __device__ __forceinline__ float ldw(const float* raw, int e) { const float w = raw[e]; return SQ ? w * w : w; }
 
-#ifndef SOT_CHUNK_UNROLL
-#define SOT_CHUNK_UNROLL 1
-#endif
 template <int G, bool SQ>
 __device__ __forceinline__ void mass_chunk_sums(const float* raw, float* part, const MassPlan& mp, int t)
 {
@@ -62,7 +59,7 @@ __device__ __forceinline__ void mass_chunk_sums(const float* raw, float* part, c
         const int s0 = h << 4;
         const int s1 = min(s0 + 16, mp.steps);
         float acc = 0.0f;
-        if (SOT_CHUNK_UNROLL && s1 - s0 == 16) {  // full chunk: issue the 16 LDS reads back to back, then the ordered adds
+        if (s1 - s0 == 16) {  // full chunk: issue the 16 LDS reads back to back, then the ordered adds
             float v[16];
 #pragma unroll
             for (int s = 0; s < 16; ++s) v[s] = ldw<SQ>(raw, ((s0 + s) << 5) + c);
@@ -78,9 +75,6 @@ __device__ __forceinline__ void mass_chunk_sums(const float* raw, float* part, c
 // Phase B: executed by 32 consecutive lanes (c = 0..31), one per column: cascade of the chunk sums
 // plus the left-over 8-lane vectors (which ATen adds to ILP group 0).  Returns the column total.
 // For n < 8 (ATen's scalar_inner_sum path) lane c == 0 returns the complete row sum instead.
-#ifndef SOT_COLUMN_PREFETCH
-#define SOT_COLUMN_PREFETCH 1   /* -0.3 us */
-#endif
 template <bool SQ>
 __device__ __forceinline__ float mass_column(const float* raw, const float* part, const MassPlan& mp, int c)
 {
@@ -94,20 +88,14 @@ __device__ __forceinline__ float mass_column(const float* raw, const float* part
     }
     float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
     const int nfull = mp.steps >> 4;
-#if SOT_COLUMN_PREFETCH
     // the first four chunk sums (all of them for n <= 2048) are fetched together: one LDS round trip instead of a
-    // dependent load -> add chain inside the serial mass fold
+    // dependent load -> add chain inside the serial mass fold (-0.3 us)
     float pre[4];
 #pragma unroll
     for (int h = 0; h < 4; ++h) pre[h] = (h < nfull) ? part[(h << 5) + c] : 0.0f;
-#endif
     int i = 0;
     for (int h = 0; h < nfull; ++h) {
-#if SOT_COLUMN_PREFETCH
         a0 = (h < 4) ? pre[h & 3] : part[(h << 5) + c];
-#else
-        a0 = part[(h << 5) + c];
-#endif
         i += 16;
         a1 += a0; a0 = 0.0f;
         if ((i & (15 << 4)) == 0) {
@@ -237,15 +225,12 @@ __device__ __forceinline__ double wave_suffix_incl_scan(double v)
 // Synchronisation of ONE row group.  A row that is owned by a single wavefront (64 threads: 129 / 257 / 512-bin rows) never
 // exchanges data with the other rows of its workgroup, and the LDS executes one wave's instructions in issue order: a
 // compiler-level ordering point is all it needs.  Rows of several wavefronts use the workgroup barrier (all row groups of a
-// workgroup execute the same number of them).  SOT_WAVE_ROWS=0 restores workgroup barriers everywhere (A/B switch).
+// workgroup execute the same number of them).
 // ---------------------------------------------------------------------------------------------
-#ifndef SOT_WAVE_ROWS
-#define SOT_WAVE_ROWS 1
-#endif
 template <int NW>
 __device__ __forceinline__ void row_sync()
 {
-    if constexpr (NW == 1 && SOT_WAVE_ROWS) {
+    if constexpr (NW == 1) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -258,7 +243,7 @@ __device__ __forceinline__ void row_sync()
 template <int NW>
 __device__ __forceinline__ bool row_any(bool flag)
 {
-    if constexpr (NW == 1 && SOT_WAVE_ROWS) {
+    if constexpr (NW == 1) {
         const bool any = __builtin_amdgcn_ballot_w64(flag) != 0ull;
         row_sync<NW>();
         return any;
@@ -721,14 +706,11 @@ __device__ __forceinline__ void merge_sort16_kv2(const SortJob& jx, const SortJo
     }
 }
 
-#ifndef SOT_MERGE_SORT
-#define SOT_MERGE_SORT 1   /* 0: the bitonic network of rounds 1-3 everywhere */
-#endif
 // the sort the kernels call: merge sort where its preconditions hold (npad >= 8, npad <= 8 MAXV T), the bitonic network otherwise
 template <int MAXV, typename Sync>
 __device__ __forceinline__ void sort_kv(float* key, int* idx, int npad, int t, int T, Sync sync)
 {
-    if (SOT_MERGE_SORT && npad >= 8 && npad <= 8 * MAXV * T) merge_sort_kv<MAXV>(key, idx, npad, t, T, sync);
+    if (npad >= 8 && npad <= 8 * MAXV * T) merge_sort_kv<MAXV>(key, idx, npad, t, T, sync);
     else bitonic_sort_kv(key, idx, npad, t, T, sync);
 }
 

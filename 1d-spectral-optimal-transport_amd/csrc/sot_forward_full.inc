@@ -14,13 +14,6 @@
 // o + (ROWS - r) * rowf: a compile-time immediate per row group (512-bin rows: four rows per 256-thread workgroup).
 // Reference semantics: losses.py:172-196, :271-313, :214-220; utils.py:135-142.
 
-// Timing-only ablations (SOT_ABLATE bits 5 / 6, results WRONG on purpose): the bank bits of every data-dependent LDS address
-// of the walk / the search are replaced by the lane number, i.e. the same instruction stream without bank conflicts.
-__device__ __forceinline__ uint32_t lane_banked(uint32_t addr)
-{
-    return (addr & ~0x7Cu) | ((threadIdx.x & 31u) << 2);
-}
-
 // Diagnostic build only (-DSOT_STAMPS): thread 0 of one workgroup adds up, per phase of its rows, the shader clocks between
 // consecutive checkpoints (sacc[i] += now - sacc[15]; sacc[15] = now) and stores the sums at the end; no output depends on them.
 #ifdef SOT_STAMPS
@@ -72,82 +65,18 @@ __device__ __forceinline__ float mass_fold_nx(const float* raw, const float* col
     return fin;
 }
 
-#ifndef SOT_FULL_SWZ
-#define SOT_FULL_SWZ 1
-#endif
-#ifndef SOT_FWD17_MIN_WAVES
-#define SOT_FWD17_MIN_WAVES 1   /* the one-wave-per-row forward kernels of 1025-bin rows (17 elements per thread): 152 / 154 VGPRs = three waves per SIMD;
-                                   held to four (128 VGPRs, spills): 16384 x 1025 paper mode 41.5 -> 77.4 us, p = 1 28.8 -> 47.0 us -- left alone */
-#endif
-// Two experiments kept behind switches (interleaved A/B on 8192 x 2048, merge kernel 44.2 us): fetching every wave total in one
-// LDS round trip instead of the wv-step load -> add loop (44.4), and issuing the first row's loads before the position copy
-// of full_setup (44.5); both together 44.8.  Neither pays: the defaults are the original forms.
-#ifndef SOT_WTOT_PREFETCH
-#define SOT_WTOT_PREFETCH 0
-#endif
-#ifndef SOT_EARLY_FIRST_FETCH
-#define SOT_EARLY_FIRST_FETCH 0
-#endif
-#ifndef SOT_MASS_BY_WAVE
-#define SOT_MASS_BY_WAVE 0   /* measured: 30.6 vs 30.3 us (merge-free kernel), 45.6 vs 45.7 (merge), 82.3 vs 81.8 (training form): no gain */
-#endif
-// Row groups of one workgroup that synchronise with the WORKGROUP barrier (rows of 2 ... 4 wavefronts, ROWS >= 2) run in lockstep
-// although they share nothing but the read-only positions: wave i of row 0 and wave i of row 1 sit on the same SIMD and reach
-// the VALU-bound walk, the LDS-bound mass phase and every barrier together.  SOT_ROW_STAGGER = K > 0 delays row group r by r * K
-// barriers (dummy barriers in front of its first row, (ROWS - 1 - r) * K behind its last one, so that every thread of the
-// workgroup executes the same number): its phases then run beside OTHER phases of its neighbour (MI355X_MICROARCH.md, "Two
-// waves per SIMD", item 9).  Results are unchanged bit for bit (the row groups never exchange data).
-// MEASURED (round 3, training form): 8192 x 2048 79.6 us -> 93.3 / 95.5 / 97.2 / 95.8 us for K = 2 / 3 / 4 / 5; 16384 x 1025
-// 85.8 -> 102 / 117 / 110 / 117 us.  The workgroup barrier makes every interval as long as the LONGER of the two phases that share
-// it, so shifted rows pay sum-of-max instead of max-of-sum: lockstep is the better schedule while the barrier is workgroup-wide
-// (gfx950 has no named barriers).  Off; kept as a switch for that one reason.
+// the one-wave-per-row forward kernels of 1025-bin rows (17 elements per thread): 152 / 154 VGPRs = three waves per SIMD; held to four
+// (128 VGPRs, spills): 16384 x 1025 paper mode 41.5 -> 77.4 us, p = 1 28.8 -> 47.0 us -- left alone
+constexpr int kFwd17MinWaves = 1;
 // Unroll factor of the merge walks in this file (trip count E is a compile-time constant, 3 ... 17).  Round 3: 32 = complete unrolling
 // (the loop-carried register moves of the partially unrolled form disappear): paper-mode forward 8192 x 2048 45.9 -> 44.1 us, training
 // form 79.7 -> 78.7 us (profiles/r3_walk_experiments_ab.txt); round 1-2 default was 2 (SOT_WALK_UNROLL of the generic kernels).
-#ifndef SOT_FULL_WALK_UNROLL
 #define SOT_FULL_WALK_UNROLL 32
-#endif
-#ifndef SOT_ROW_STAGGER
-#define SOT_ROW_STAGGER 0
-#endif
-#ifndef SOT_BWD_LOSER
-#define SOT_BWD_LOSER 0
-#endif
-// (Round 3, two negative results on the merge phases, profiles/r3_walk_experiments_ab.txt:
-//  * SOT_BWD_LOSER = 1, the backward walk in loser form with the canonical tie order kept by a scalar lane mask -- about 5 VALU
-//    instructions fewer per step, a few scalar ones more: training form 79.6 -> 79.5 us (8192 x 2048), 86.2 -> 85.9 us (16384 x 1025),
-//    both-gradient backward 91.8 -> 93.4 us.  Correct (all tests pass with it), no gain: off.
-//  * two / three / four shorter merge segments per thread in the forward kernel, their search and walk chains interleaved (more
-//    independent LDS round trips in flight per wave): paper-mode forward 45.8 -> 49.1 / 54.3 / 57.8 us.  The extra partition searches
-//    cost more than the shorter chains save: these phases are bound by instructions issued, not by the latency of their chains.
-//    That code was removed again.)
+// (Round 3: two / three / four shorter merge segments per thread in the forward kernel, their search and walk chains interleaved, were
+// slower -- paper-mode forward 45.8 -> 49.1 / 54.3 / 57.8 us: these phases are bound by instructions issued, not by the latency of their chains.)
 
-template <int ROWS, int NW>
-__device__ __forceinline__ void stagger_barriers(int count)
-{
-    if constexpr (ROWS > 1 && NW > 1 && (SOT_ROW_STAGGER > 0)) {
-        for (int k = 0; k < count * SOT_ROW_STAGGER; ++k) __syncthreads();
-    }
-}
-
-#ifndef SOT_FWD_1025_ONEWAVE_ROWS
-#define SOT_FWD_1025_ONEWAVE_ROWS 6144   /* batches of at least this many 1025-bin rows: one wave per row in the forward kernel (0: never) */
-#endif
-#ifndef SOT_AREA_HALF_WAVE
-#define SOT_AREA_HALF_WAVE 1   /* merge-free kernel, two rows per wave (sot_area_half_kernel): 1 = 129-bin rows, 2 = 257-bin rows as well */
-#endif
-#ifndef SOT_FWD_HALF_WAVE
-#define SOT_FWD_HALF_WAVE 1    /* large batches of 129- / 257-bin rows in the merge forward: two rows per wave (sot_forward_half_kernel) */
-#endif
-#ifndef SOT_RT_MID_CAPACITIES
-#define SOT_RT_MID_CAPACITIES 1
-#endif
-#ifndef SOT_RT_1024_ONEWAVE_ROWS
-#define SOT_RT_1024_ONEWAVE_ROWS 8192    /* the same for run-time lengths on the 1024-point geometry (16 elements per thread) */
-#endif
-#ifndef SOT_FULL_LATE_FETCH
-#define SOT_FULL_LATE_FETCH 1   /* 8192x2048: 45.6 -> 44.8 us */
-#endif
+constexpr int kFwd1025OneWaveRows = 6144;   // batches of at least this many 1025-bin rows: one wave per row in the forward kernel
+constexpr int kRt1024OneWaveRows = 8192;    // the same for run-time lengths on the 1024-point geometry (16 elements per thread)
 
 // merge_path_steps32() of sot_device.hpp with compile-time lengths: the rounds unroll completely and the probe offsets
 // fold into the LDS instructions (5 VALU per round).  ub1 = LDS address of U[-1], vd1 = LDS address of V[D] + ub1; returns
@@ -166,13 +95,8 @@ __device__ __forceinline__ uint32_t merge_path_fixed32(uint32_t ub1, uint32_t vd
     for (int k = TOPK; k >= -1; --k) {
         const uint32_t step4 = 4u * (uint32_t)(k >= 1 ? (1 << k) + 1 : (k == 0 ? 2 : 1));  // ..., 9, 5, 3, 2, 1
         const uint32_t candb = posb + step4;          // address of U[cand - 1]
-#if SOT_ABLATE & 64
-        const float u = lds_load(lane_banked(candb));
-        const float v = lds_load(lane_banked(vd1 - candb));
-#else
         const float u = lds_load(candb);
         const float v = lds_load(vd1 - candb);        // V[D - cand]
-#endif
         const int take = (int)(candb <= hib) & (int)(u <= v);  // bitwise: no branch around the LDS reads
         posb = take ? candb : posb;
     }
@@ -199,12 +123,8 @@ __device__ __forceinline__ void fetch_row_dwords(const float* __restrict__ x, co
 // row returns 0, a store past it is dropped, per dword -- also inside a merged multi-dword access (the ISA range-checks
 // load/store_dwordx{2,3,4} per component) -- so rows whose length is not the geometry's need neither predicates nor branches around
 // their memory instructions, and an address is one 32-bit byte offset instead of a 64-bit pointer per element.
-#ifndef SOT_ROW_BUFFERS
-#define SOT_ROW_BUFFERS 1   /* 0: predicated global loads / stores (the round-3a form).  Training form, interleaved A/B, bit-identical results:
-                               run-time lengths 8192 x 2000 109.0 -> 106.5 us, 16384 x 1000 96.7 -> 95.3 us.  For the compile-time odd lengths the
-                               same stores change nothing (1025 bins: 84.8 vs 84.8 us, 257: 25.4 vs 25.3) or lose (513 bins: 24.7 -> 26.2 us), so
-                               those keep their predicated stores. */
-#endif
+// Against predicated global loads / stores (training form, run-time lengths): 8192 x 2000 109.0 -> 106.5 us.  For the compile-time odd
+// lengths the same stores change nothing or lose (513 bins: 24.7 -> 26.2 us), so those keep their predicated stores.
 typedef __amdgpu_buffer_rsrc_t RowBuffer;
 __device__ __forceinline__ RowBuffer row_buffer(const float* row, int n)
 {
@@ -224,22 +144,12 @@ template <int G, int CPT>
 __device__ __forceinline__ void fetch_row_dwords_rt(const float* __restrict__ x, const float* __restrict__ y, int t, int n, float (&rx)[CPT],
                                                     float (&ry)[CPT])
 {
-#if SOT_ROW_BUFFERS
     const RowBuffer bx = row_buffer(x, n), by = row_buffer(y, n);
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
         rx[k] = row_buffer_load(bx, t + k * G);
         ry[k] = row_buffer_load(by, t + k * G);
     }
-#else
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int e = t + k * G;
-        const bool ok = e < n;
-        rx[k] = ok ? x[e] : 0.0f;
-        ry[k] = ok ? y[e] : 0.0f;
-    }
-#endif
 }
 
 // one row's loads in the form its geometry takes (NX == 0: 16-B loads, NX > 0: dword loads with a compile-time length, NX < 0: run time)
@@ -268,15 +178,8 @@ __device__ __forceinline__ void fetch_full_row(const float* __restrict__ x, cons
 // both arrays): the chunk sums no longer read the staged row back from LDS (16 ds_read_b32 per thread) and the workgroup barrier between
 // staging and chunk sums is gone; 16 dword loads and 16 ds_write_b32 per thread instead of 4 + 4 sixteen-byte ones.
 // rx[k] = step k, ry[k] = step 8 + k of the thread's task (both of ONE array).
-#ifndef SOT_COLUMN_FETCH
-#define SOT_COLUMN_FETCH 1
-#endif
-constexpr bool kColumnFetch = (SOT_COLUMN_FETCH != 0) && !(SOT_ABLATE & 4);   // (timing-only ablation bit 2 removes the mass phase: float4 form)
 // forward kernels in square_dist mode stage the SQUARED weights (the chunk sums need the squares anyway; the owner's division then reads
 // them instead of squaring again); the backward kernels keep the raw weights (their output arithmetic needs them)
-#ifndef SOT_STAGE_SQUARES
-#define SOT_STAGE_SQUARES 1
-#endif
 template <int G, int CPT>
 __device__ __forceinline__ void fetch_row_columns(const float* __restrict__ x, const float* __restrict__ y, int t, float (&rx)[CPT], float (&ry)[CPT])
 {
@@ -292,12 +195,6 @@ __device__ __forceinline__ void fetch_row_columns(const float* __restrict__ x, c
 // of both arrays are one per thread (two for the one-wave rows of 1025 bins), a task has CHUNK = min(16, NSTEPS) steps, and the row's last
 // element (N mod 8 == 1: ATen's scalar tail) is fetched by thread 0 (x) / thread 1 (y).  Register j of the thread's TPT * CHUNK (+ 1) values
 // is rx[j] for j < CPT and ry[j - CPT] above.
-#ifndef SOT_COLUMN_FETCH_NX
-#define SOT_COLUMN_FETCH_NX 1
-#endif
-#ifndef SOT_COLUMN_FETCH_NX_MIN_BINS
-#define SOT_COLUMN_FETCH_NX_MIN_BINS 1025
-#endif
 template <int G, int CPT, int N>
 struct ColumnsNX {
     static constexpr int NSTEPS = N >> 5, NCH = (NSTEPS + 15) >> 4, NT = 32 * NCH, CHUNK = NSTEPS < 16 ? NSTEPS : 16;
@@ -307,8 +204,8 @@ struct ColumnsNX {
     // 29.0 -> 28.2 us, 4096 x 2049 forward 26.0 -> 25.1 us; the training kernels do not move (79.7 vs 79.8 us); the short one-wave rows LOSE
     // (16384 x 257 forward 15.2 -> 16.8 us, 8192 x 513 training 24.8 -> 25.6 us: 8 / 16 dword loads per thread instead of 5 / 9 for the same bytes):
     // 1025 bins and up only.
-    static constexpr bool OK = (SOT_COLUMN_FETCH_NX != 0) && kColumnFetch && (2 * NT) % G == 0 && TPT >= 1 && NV + 1 <= 2 * CPT && (N & 7) == 1 &&
-                               N >= SOT_COLUMN_FETCH_NX_MIN_BINS;
+    static constexpr int MIN_BINS = 1025;
+    static constexpr bool OK = (2 * NT) % G == 0 && TPT >= 1 && NV + 1 <= 2 * CPT && (N & 7) == 1 && N >= MIN_BINS;
 };
 template <int CPT>
 __device__ __forceinline__ float& column_slot(float (&rx)[CPT], float (&ry)[CPT], int j) { return j < CPT ? rx[j] : ry[j - CPT]; }
@@ -334,7 +231,7 @@ __device__ __forceinline__ void fetch_row_columns_nx(const float* __restrict__ x
 template <int G, int CPT, int NX>
 __device__ __forceinline__ void fetch_row(const float* __restrict__ x, const float* __restrict__ y, int t, int n, float (&rx)[CPT], float (&ry)[CPT])
 {
-    if constexpr (NX == 0 && kColumnFetch) fetch_row_columns<G, CPT>(x, y, t, rx, ry);
+    if constexpr (NX == 0) fetch_row_columns<G, CPT>(x, y, t, rx, ry);
     else if constexpr (NX > 0 && ColumnsNX<G, CPT, (NX > 0 ? NX : 129)>::OK) fetch_row_columns_nx<G, CPT, NX>(x, y, t, rx, ry);
     else if constexpr (NX == 0) fetch_full_row<G, CPT>(x, y, t, rx, ry);
     else if constexpr (NX > 0) fetch_row_dwords<G, CPT, NX>(x, y, t, rx, ry);
@@ -379,7 +276,7 @@ __host__ __device__ constexpr FullLayout full_layout()
     L.grad = align4(L.red + NW + 4);
     L.goff = GRAD == 2 ? L.grad - L.nU : L.grad;
     L.rowf = GRAD == 2 ? L.grad + L.nV : GRAD ? L.grad + L.nU + L.nV : L.grad;
-    L.posf = (SOT_ABLATE & 128) ? 0 : L.nU + L.nV;   // ablation bit 7 (timing only): no position copy in LDS -> more rows per CU
+    L.posf = L.nU + L.nV;
     L.total = ROWS * L.rowf + L.posf;
     return L;
 }
@@ -395,7 +292,7 @@ struct FullGeo {
     static constexpr int NSTEPS = N >> 5;            // ATen: steps of each of the 32 columns
     static_assert(N <= CAP && N >= 64 && CPT >= 2 && CPT <= 17, "the row fits its geometry");
     static_assert(!ALIGNED || CPT == 8, "rows that fill their geometry: 8 contiguous elements (two 16-B halves) per thread");
-    static constexpr bool SWZ = (SOT_FULL_SWZ != 0) && CPT == 8 && !RT;   // staging swizzle (see full_build_cdfs): 8-element owners only
+    static constexpr bool SWZ = CPT == 8 && !RT;   // staging swizzle (see full_build_cdfs): 8-element owners only
     static_assert(NX <= 0 || CAP - N >= 1, "NX is for rows shorter than the capacity");
     static_assert(RT || NSTEPS < 16 || NSTEPS % 16 == 0, "every column is either one partial chunk or whole 16-step chunks");
     static_assert(RT || (N >> 3) == NSTEPS * 4, "no left-over 8-lane vectors (N mod 32 < 8)");
@@ -453,7 +350,7 @@ __device__ __forceinline__ FullCtx full_setup(const FwdArgs& a, float* smem)
     float* const PY = smem + ROWS * L.rowf + L.nU;
     c.PX = PX; c.PY = PY;
     const int nlast = (Geo::RT ? a.n : N) - 1;    // index of the row's last real point
-    if (!(SOT_ABLATE & 128) && !RP) {   // (RP: every row brings its own positions, see sot_forward_full_kernel)
+    if (!RP) {   // (RP: every row brings its own positions, see sot_forward_full_kernel)
 #pragma unroll
         for (int e = tid; e < N; e += Geo::BLOCK) {   // run-time length: the points past the row sit at its last position
             const int es = Geo::RT ? min(e, nlast) : e;
@@ -486,21 +383,14 @@ __device__ __forceinline__ FullCtx full_setup(const FwdArgs& a, float* smem)
 template <int E, int PM, bool LIM, uint32_t POFF4>
 __device__ __forceinline__ float merge_walk_full(uint32_t ou, uint32_t ov, bool first, float p)
 {
-#if SOT_ABLATE & 32
-#define SOT_LD(off) lds_load(lane_banked(off))
-#else
-#define SOT_LD(off) lds_load(off)
-#endif
-    float w = SOT_LD(ou), wp = SOT_LD(ou + POFF4);
-    float r = SOT_LD(ov), rp = SOT_LD(ov + POFF4);
-    float qprev = fmaxf(SOT_LD(ou - 4u), SOT_LD(ov - 4u));
+    float w = lds_load(ou), wp = lds_load(ou + POFF4);
+    float r = lds_load(ov), rp = lds_load(ov + POFF4);
+    float qprev = fmaxf(lds_load(ou - 4u), lds_load(ov - 4u));
     if (first) qprev = 0.0f;  // Q_0 := 0 (the pad of losses.py:301)
     uint32_t pw = ou + 4u, pr = ov + 4u;  // next unread element of w's / r's stream
     float acc = 0.0f;
-#if SOT_FULL_WALK_UNROLL > 0
 #pragma unroll SOT_FULL_WALK_UNROLL
-#endif
-    for (int s2 = 0; s2 < ((SOT_ABLATE & 1) ? 1 : E); ++s2) {
+    for (int s2 = 0; s2 < E; ++s2) {
         const bool c = w <= r;
         const float q = c ? w : r;
         const float cost = transport_cost<PM>(wp, rp, p);
@@ -513,10 +403,9 @@ __device__ __forceinline__ float merge_walk_full(uint32_t ou, uint32_t ov, bool 
         pw = nx + 4u;
         r = c ? r : w;
         rp = c ? rp : wp;
-        w = SOT_LD(nx);
-        wp = SOT_LD(nx + POFF4);
+        w = lds_load(nx);
+        wp = lds_load(nx + POFF4);
     }
-#undef SOT_LD
     return acc;
 }
 
@@ -527,7 +416,7 @@ __device__ __forceinline__ float merge_walk_full(uint32_t ou, uint32_t ov, bool 
 // nothing is written to U / V and the closing barrier is left out (the barrier behind the raw reads already orders the next
 // row's staging behind this row's last LDS read of the raw weights).
 // RAW_OUT: wx / wy must be the weights as given (a gradient needs them); otherwise square_dist rows may be staged as their squares
-template <int G, int CPT, int ROWS, int GRAD, bool SQ, int NX = 0, bool TO_LDS = true, bool LATE_FETCH = (SOT_FULL_LATE_FETCH != 0), bool RAW_OUT = (GRAD != 0)>
+template <int G, int CPT, int ROWS, int GRAD, bool SQ, int NX = 0, bool TO_LDS = true, bool RAW_OUT = (GRAD != 0)>
 __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx& c, float (&rx)[CPT], float (&ry)[CPT],
                                                 const float* nxt_x, const float* nxt_y, float (&wx)[CPT], float (&wy)[CPT],
                                                 float& Sx, float& Sy, float (&cu)[CPT], float (&cv)[CPT], unsigned long long* sacc = nullptr,
@@ -540,7 +429,6 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     using Geo = FullGeo<G, CPT, ROWS, GRAD, NX>;
     constexpr int N = Geo::N, NW = Geo::NW, NT = Geo::NT, CHUNK = Geo::CHUNK;
     constexpr bool ALIGNED = Geo::ALIGNED, RT = Geo::RT;
-    constexpr bool LATE = LATE_FETCH;  // see the fetch below
     float* const U = c.U; float* const V = c.V; float* const part = c.part; float* const colbuf = c.colbuf;
     double* const wtot = c.wtot; float* const Sv = c.Sv;
     const int t = c.t, lane = c.lane, wv = c.wv;
@@ -556,8 +444,8 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     const int ownf = SWZ ? ((t >> 2) & 1) : 0;       // this thread's 8 owned elements sit in a swapped block
     // ---- P1: registers -> LDS in original column order; fetch the next row into the registers
     constexpr bool COLUMNS_NX = (NX > 0) && ColumnsNX<G, CPT, (NX > 0 ? NX : 129)>::OK;   // fetch_row_columns_nx
-    constexpr bool COLUMNS = (ALIGNED && kColumnFetch) || COLUMNS_NX;   // staging and chunk sum of the thread's own task(s)
-    constexpr bool PRESQ = COLUMNS && SQ && !RAW_OUT && (SOT_STAGE_SQUARES != 0);   // the staged values are the squares
+    constexpr bool COLUMNS = ALIGNED || COLUMNS_NX;   // staging and chunk sum of the thread's own task(s)
+    constexpr bool PRESQ = COLUMNS && SQ && !RAW_OUT;   // the staged values are the squares
     if constexpr (COLUMNS_NX) {
         using C = ColumnsNX<G, CPT, (NX > 0 ? NX : 129)>;
         static_assert(!COLUMNS_NX || (C::NT == NT && C::CHUNK == CHUNK && !SWZ), "the task layout of the chunk sums below");
@@ -610,49 +498,20 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
             if (RT || (k * G < N && (((k + 1) * G <= N) || (t + k * G < N)))) { U[es + k * G] = rx[k]; V[es + k * G] = ry[k]; }
         }
     }
-    if (!LATE && nxt_x != nullptr) fetch_row<G, CPT, NX>(nxt_x, nxt_y, t, a.n, rx, ry);
     SOT_PH(sacc, 1);   // staging stores issued (includes the wait for this row's loads)
     row_sync<NW>();
     SOT_PH(sacc, 2);   // barrier 1
 
-    // ---- P2: row masses in ATen order (sot_device.hpp).  Rows of 2 ... 4 wavefronts (SOT_MASS_BY_WAVE): wave 0 computes the
-    //      whole mass of x, wave 1 that of y -- chunk sums, columns and fold chained through wave-level ordering points --
-    //      so that the workgroup barrier between the chunk sums and the fold disappears (every barrier of a row costs each
-    //      wave ~700 cycles of waiting for its slowest sibling, tools/area_stamps.py).  Larger rows spread the chunk sums
-    //      over all threads as before.
-    constexpr bool MASS_BY_WAVE = (SOT_MASS_BY_WAVE != 0) && NW >= 2 && NW <= 4 && !(SOT_ABLATE & 4) && !RT;
+    // ---- P2: row masses in ATen order (sot_device.hpp)
     const MassPlan mp = make_mass_plan(RT ? a.n : N);   // used by the run-time-length rows only
     if constexpr (COLUMNS) {
         // chunk sums came out of the fetched registers in P1
     } else if constexpr (RT) {   // the summation plan follows the REAL length: the generic chunk sums (sot_device.hpp), x then y
         mass_chunk_sums<G, SQ>(U, part, mp, t);
         if (!dn) mass_chunk_sums<G, SQ>(V, part + NT, mp, t);
-    } else if constexpr (MASS_BY_WAVE) {
-        if (wv < 2 && !(wv == 1 && dn)) {
-            const float* const rawm = wv ? V : U;
-            float* const partw = part + wv * NT;
-#pragma unroll
-            for (int task0 = 0; task0 < NT; task0 += kWave) {
-                const int task = task0 + lane;
-                if (NT % kWave == 0 || task < NT) {
-                    const float* src = rawm + ((task >> 5) << 9) + (task & 31);
-                    const float* srco = rawm + ((task >> 5) << 9) + ((task & 31) ^ (SWZ ? 4 : 0));  // odd steps: bit 5 set
-                    float v[CHUNK];
-#pragma unroll
-                    for (int s2 = 0; s2 < CHUNK; ++s2) { const float w = ((s2 & 1) ? srco : src)[s2 << 5]; v[s2] = SQ ? w * w : w; }
-                    float acc = 0.0f;
-#pragma unroll
-                    for (int s2 = 0; s2 < CHUNK; ++s2) acc += v[s2];
-                    partw[task] = acc;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
     } else {
 #pragma unroll
-    for (int id0 = 0; id0 < ((SOT_ABLATE & 4) ? 0 : 2 * NT); id0 += G) {
+    for (int id0 = 0; id0 < 2 * NT; id0 += G) {
         const int id = id0 + t;
         const bool isy = id >= NT;
         if (id < 2 * NT && !(isy && dn)) {
@@ -670,13 +529,11 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     }
     }
     SOT_PH(sacc, 3);   // chunk sums
-    if constexpr (!MASS_BY_WAVE && !COLUMNS) row_sync<NW>();
+    if constexpr (!COLUMNS) row_sync<NW>();
     SOT_PH(sacc, 4);   // barrier 2
     // ... columns + fold by one wave per array (wave 0: x, wave 1: y; a one-wave row uses its half-waves)
-    __builtin_amdgcn_s_setprio(SOT_MASS_PRIO);
-    if (SOT_ABLATE & 4) {
-        if (t < 4) Sv[t] = 1.0f;
-    } else if (NW >= 2) {
+    __builtin_amdgcn_s_setprio(kMassPrio);
+    if (NW >= 2) {
         if (wv < 2 && !(wv == 1 && dn)) {
             const float* raw = wv ? V : U;
             float* cb = colbuf + 32 * wv;
@@ -767,12 +624,10 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
         uint32_t risk = 0xFFFFFFFFu;
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
-            if (SOT_ABLATE & 8) { qx[k] = wx[k] * rSx; qy[k] = wy[k] * rSy; continue; }
             qx[k] = div_by_row_constant((SQ && !PRESQ) ? wx[k] * wx[k] : wx[k], Sxh, rSx, risk);
             qy[k] = div_by_row_constant((SQ && !PRESQ) ? wy[k] * wy[k] : wy[k], Syh, rSy, risk);
         }
         const bool slow = (risk < kFastDivMinBits) || !(Sxh <= 0x1p40f) || !(Syh <= 0x1p40f);
-#ifndef SOT_NO_DIV_FALLBACK   /* diagnostic: register-pressure experiments only */
         if (__builtin_amdgcn_ballot_w64(slow) != 0ull) {  // rare, wave-uniform (see build_cdfs)
             asm volatile("; IEEE division fallback" ::: "memory");
 #pragma unroll
@@ -781,35 +636,21 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
                 qy[k] = ((SQ && !PRESQ) ? wy[k] * wy[k] : wy[k]) / Syh;
             }
         }
-#endif
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
             runx += (double)qx[k]; runy += (double)qy[k];
             px[k] = runx; py[k] = runy;
         }
     }
-    const double inx = (SOT_ABLATE & 16) ? runx : wave_incl_scan(runx), iny = (SOT_ABLATE & 16) ? runy : wave_incl_scan(runy);
-    double exx = (SOT_ABLATE & 16) ? 0.0 : wave_shift_right1(inx), exy = (SOT_ABLATE & 16) ? 0.0 : wave_shift_right1(iny);
+    const double inx = wave_incl_scan(runx), iny = wave_incl_scan(runy);
+    double exx = wave_shift_right1(inx), exy = wave_shift_right1(iny);
     if (NW > 1 && lane == kWave - 1) { wtot[wv] = inx; wtot[NW + wv] = iny; }
     SOT_PH(sacc, 7);   // division, fp64 accumulation, wave scans
     row_sync<NW>();  // raw weights are consumed, wave totals are visible
     SOT_PH(sacc, 8);   // barrier 4
     if constexpr (NW > 1) {
-#if SOT_WTOT_PREFETCH
-        // totals of the waves in front of this one, added in wave order; every total is fetched up front (independent
-        // LDS reads: one round trip) instead of a dependent load -> add chain of wv steps
-        double tx[NW > 1 ? NW - 1 : 1], ty[NW > 1 ? NW - 1 : 1];
-#pragma unroll
-        for (int w = 0; w < NW - 1; ++w) { tx[w] = wtot[w]; ty[w] = wtot[NW + w]; }
-        double ox = 0.0, oy = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW - 1; ++w) {
-            if (w < wv) { ox += tx[w]; oy += ty[w]; }
-        }
-#else
         double ox = 0.0, oy = 0.0;
         for (int w = 0; w < wv; ++w) { ox += wtot[w]; oy += wtot[NW + w]; }
-#endif
         exx += ox; exy += oy;
     }
 #pragma unroll
@@ -828,9 +669,9 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
             }
         }
     }
-    // LATE: the next row's loads are issued here (not in P1): their 2*CPT destination registers are then live only
-    // during the merge phases, whose register demand is small, instead of across the register-hungry division / scan
-    if (LATE && nxt_x != nullptr) fetch_row<G, CPT, NX>(nxt_x, nxt_y, t, a.n, rx, ry);
+    // the next row's loads are issued here (not in P1): their 2*CPT destination registers are then live only during the merge
+    // phases, whose register demand is small, instead of across the register-hungry division / scan (8192 x 2048: 45.6 -> 44.8 us)
+    if (nxt_x != nullptr) fetch_row<G, CPT, NX>(nxt_x, nxt_y, t, a.n, rx, ry);
     if constexpr (TO_LDS) row_sync<NW>();
 }
 
@@ -851,14 +692,10 @@ __device__ __forceinline__ void owner_perm_slots(const FwdArgs& a, const int* pe
 // Geometry experiments on 8192 x 2048 (all slower than one 256-thread row per workgroup, 4 workgroups per CU, 44.8 us):
 // two rows per 512-thread workgroup sharing the positions: 46.5 us at the same 4 rows per CU; held to 96 VGPRs 52.3 us,
 // to 80 VGPRs (6 rows per CU, 26 dwords spilled) 74 us; 512 threads x 4 elements per row 53-54 us.
-#ifndef SOT_FWD_MIN_WAVES
-#define SOT_FWD_MIN_WAVES 1
-#endif
+constexpr int kFwdMinWaves = 1;
 // (The run-time-length kernel of the 4096-point geometry came out at 129 VGPRs: one 512-thread workgroup per CU instead of the two its LDS allows;
 //  held to 128 -- four waves per SIMD -- 4096 x 4000 paper mode: see profiles/r4p_segmented_sort.txt, "register steps".)
-#ifndef SOT_RT512_MIN_WAVES
-#define SOT_RT512_MIN_WAVES 4
-#endif
+constexpr int kRt512MinWaves = 4;
 
 // RP (per-row positions through handed-over permutations, see sot_forward_full_kernel): row `rowc`'s sorted positions into the position copy behind
 // the row region, its permutations into ix / iy (original columns of the thread's CPT owned sorted elements) and psx / psy (their staged LDS indices).
@@ -907,7 +744,7 @@ __device__ __forceinline__ void rowpos_row_setup(const FwdArgs& a, const FullCtx
 // position copy behind the row region -- and its weights are read through the same permutation (the psx / psy path of a permuted shared grid).
 // One row per workgroup only (the position copy is the row's own), rows that fill their geometry (NX == 0).
 template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX = 0, bool RP = false>
-__global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVES : (CPT == 17) ? SOT_FWD17_MIN_WAVES : SOT_FWD_MIN_WAVES) void sot_forward_full_kernel(const FwdArgs a)
+__global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? kRt512MinWaves : (CPT == 17) ? kFwd17MinWaves : kFwdMinWaves) void sot_forward_full_kernel(const FwdArgs a)
 {
     static_assert(!RP || (ROWS == 1 && NX == 0 && CPT == 8), "per-row positions: one row per workgroup, rows that fill the 8-element geometry");
     using Geo = FullGeo<G, CPT, ROWS, false, NX>;
@@ -917,13 +754,6 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVE
     const int64_t row_step = (int64_t)gridDim.x * ROWS;
     int64_t row0 = (int64_t)blockIdx.x * ROWS;
     float rx[CPT], ry[CPT];
-#if SOT_EARLY_FIRST_FETCH
-    if (row0 < a.B) {   // the first row's loads go out BEFORE the position copy of full_setup: one memory round trip, not two
-        const int rg0 = (int)threadIdx.x / G, t0 = (int)threadIdx.x - rg0 * G;
-        const int64_t r = min(row0 + rg0, a.B - 1);
-        fetch_row<G, CPT, NX>(a.x + r * a.xs, a.y + r * a.ys, t0, a.n, rx, ry);
-    }
-#endif
     FullCtx cm = full_setup<G, CPT, ROWS, false, NX, RP>(a, smem);
     if constexpr (RP) { cm.x_ident = false; cm.y_ident = false; }
     const FullCtx c = cm;
@@ -931,12 +761,10 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVE
     const int rg = c.rg, t = c.t, lane = c.lane, wv = c.wv;
     float* const V = c.V; float* const red = c.red;
     const float* const Uw = c.Uw;
-#if !SOT_EARLY_FIRST_FETCH
     if (row0 < a.B) {
         const int64_t r = min(row0 + rg, a.B - 1);
         fetch_row<G, CPT, NX>(a.x + r * a.xs, a.y + r * a.ys, t, a.n, rx, ry);
     }
-#endif
 
 #ifdef SOT_STAMPS
     unsigned long long sbuf[16] = {};
@@ -951,7 +779,6 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVE
         if (!c.x_ident) owner_perm_slots<G, CPT, ROWS, NX>(a, a.xperm, t, psx);
         if (!c.y_ident) owner_perm_slots<G, CPT, ROWS, NX>(a, a.yperm, t, psy);
     }
-    stagger_barriers<ROWS, NW>(rg);
     for (; row0 < a.B; row0 += row_step) {
         const int64_t row = row0 + rg;
         const bool valid = row < a.B;
@@ -973,7 +800,7 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVE
 
         // ---- P4: merge of the two CDFs (losses.py:295-313), E steps per thread
         float acc = 0.0f;
-        __builtin_amdgcn_s_setprio(SOT_WALK_PRIO);
+        __builtin_amdgcn_s_setprio(kWalkPrio);
         // (Thread t merges segment t.  Permuting the segments over the lanes -- segment 19 t mod G etc., to change the LDS bank
         // pattern of the walk -- was measured 1.5-6 % slower for ten multipliers; E = 16 instead of 17 is 13 % slower.)
         if (GA == G || t < GA) {
@@ -982,15 +809,11 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVE
             (void)VOFF;
             const uint32_t ub1 = lds_addr(Uw) - 4u;                        // address of Uw[-1]
             const uint32_t vd1 = lds_addr(V) + 4u * (uint32_t)D0 + ub1;    // address of V[D0], + ub1
-#if SOT_ABLATE & 2
-            const uint32_t pb = ub1 + 4u * (uint32_t)min(D0 >> 1, N + PAD);
-#else
             const uint32_t pb = merge_path_fixed32<N + PAD, N>(ub1, vd1, D0);  // address of Uw[i0 - 1]
-#endif
             SOT_PH(sacc, 10);  // partition search
             const uint32_t ou = pb + 4u;     // address of Uw[i0]
             const uint32_t ov = vd1 - pb;    // address of V[D0 - i0]
-            constexpr uint32_t ROWB = (SOT_ABLATE & 128) ? 0u : 4u * (uint32_t)L.rowf;  // the positions lie (ROWS - rg) row regions behind this row
+            constexpr uint32_t ROWB = 4u * (uint32_t)L.rowf;  // the positions lie (ROWS - rg) row regions behind this row
             if (ROWS == 1 || rg == ROWS - 1) acc = merge_walk_full<E, PM, LIM, ROWB>(ou, ov, D0 == 0, a.p);
             else if (ROWS == 2 || rg == ROWS - 2) acc = merge_walk_full<E, PM, LIM, 2u * ROWB>(ou, ov, D0 == 0, a.p);
             else if (ROWS == 3 || rg == ROWS - 3) acc = merge_walk_full<E, PM, LIM, 3u * ROWB>(ou, ov, D0 == 0, a.p);
@@ -1020,7 +843,6 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVE
 #ifdef SOT_STAMPS
     if (sacc != nullptr) { for (int i = 0; i < 16; ++i) g_stamps[i] = sacc[i]; }
 #endif
-    stagger_barriers<ROWS, NW>(ROWS - 1 - rg);
     if (a.mt.counters != nullptr) batch_mean_tail<ROWS * G>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
 }
 
@@ -1041,14 +863,9 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? SOT_RT512_MIN_WAVE
 // The row pipeline shrinks to staging, ATen-ordered masses, division, fp64 scans and one fused multiply-add per element:
 // 5 barriers per row instead of 8, 18 KB of LDS per 2048-bin row instead of 34.5 KB.
 // ---------------------------------------------------------------------------------------------
-#ifndef SOT_AREA_MIN_WAVES
-#define SOT_AREA_MIN_WAVES 1
-#endif
-#ifndef SOT_AREA_LATE_FETCH
-#define SOT_AREA_LATE_FETCH 1   /* 0: the next row's loads are issued right after this row is staged (in flight for the whole row): 30.9 vs 30.3 us */
-#endif
+constexpr int kAreaMinWaves = 1;
 template <int G, int CPT, int ROWS, bool SQ, int NX = 0>
-__global__ __launch_bounds__(ROWS * G, (CPT == 17) ? SOT_FWD17_MIN_WAVES : SOT_AREA_MIN_WAVES) void sot_area_full_kernel(const FwdArgs a)
+__global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWaves) void sot_area_full_kernel(const FwdArgs a)
 {
     using Geo = FullGeo<G, CPT, ROWS, false, NX>;
     constexpr FullLayout L = Geo::L;
@@ -1103,11 +920,11 @@ __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? SOT_FWD17_MIN_WAVES : SOT_A
         float Sx, Sy;
 #ifdef SOT_STAMPS
         if (sacc != nullptr) sacc[15] = __builtin_readcyclecounter();
-        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, (SOT_AREA_LATE_FETCH != 0)>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
                                                             more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc);
         SOT_PH(sacc, 9);   // wave totals, CDF values, next row's loads issued
 #else
-        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, (SOT_AREA_LATE_FETCH != 0)>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
                                                             more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv);
 #endif
         float acc = 0.0f;
@@ -1380,12 +1197,9 @@ static hipError_t launch_area_full(const FwdArgs& a, hipStream_t s)
     const size_t lds = sizeof(float) * (size_t)ROWS * (size_t)L.rowf;
     constexpr int block = ROWS * G;
     static GridCache cache;
-    int grid_cap = cached_resident_grid(cache, kern, block, lds);
-#ifdef SOT_AREA_GRID_CAP   /* diagnostic: another number of workgroups */
-    grid_cap = SOT_AREA_GRID_CAP;
-#endif
+    const int grid_cap = cached_resident_grid(cache, kern, block, lds);
     const int64_t want = (a.B + ROWS - 1) / ROWS;
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();
     launch_maybe_profiled(kern, grid, block, lds, s, a);
     return hipGetLastError();
@@ -1408,11 +1222,11 @@ static hipError_t dispatch_area_half(const FwdArgs& a, hipStream_t s)
     if (a.flags & SOT_FLAG_SQUARE) {
         auto kern = sot_area_half_kernel<CPT, ROWS, true, N>;
         static GridCache cache;
-        launch_maybe_profiled(kern, balanced_grid(want, cached_resident_grid(cache, kern, block, lds)), block, lds, s, a);
+        launch_maybe_profiled(kern, persistent_grid(want, cached_resident_grid(cache, kern, block, lds)), block, lds, s, a);
     } else {
         auto kern = sot_area_half_kernel<CPT, ROWS, false, N>;
         static GridCache cache;
-        launch_maybe_profiled(kern, balanced_grid(want, cached_resident_grid(cache, kern, block, lds)), block, lds, s, a);
+        launch_maybe_profiled(kern, persistent_grid(want, cached_resident_grid(cache, kern, block, lds)), block, lds, s, a);
     }
     return hipGetLastError();
 }
@@ -1428,11 +1242,9 @@ hipError_t dispatch_area_full(const FwdArgs& a, hipStream_t s)
         case 4096: return dispatch_area_full_g<512, 8, 1>(a, s);
         case 8192: return dispatch_area_full_g<1024, 8, 1>(a, s);
         case 129:   // two rows per wave: 65536 rows 25.3 -> 20.6 us, 4096 rows 7.9 -> 7.7 us
-            if (SOT_AREA_HALF_WAVE) return dispatch_area_half<5, 8, 129>(a, s);
-            return dispatch_area_full_g<64, 3, 4, 129>(a, s);
+            return dispatch_area_half<5, 8, 129>(a, s);
         case 2049: return dispatch_area_full_g<256, 9, 1, 2049>(a, s);
         case 257:   // (two rows per wave: 65536 rows 33.0 -> 32.0 us, 16384 rows 10.2 -> 10.8 us: this kernel is at the HBM limit for 257-bin rows already)
-            if (SOT_AREA_HALF_WAVE == 2) return dispatch_area_half<9, 8, 257>(a, s);
             return dispatch_area_full_g<64, 5, 4, 257>(a, s);
         case 513: return dispatch_area_full_g<64, 9, 4, 513>(a, s);
         case 1025:   // one wave per row (17 elements per thread, no workgroup barrier): 1024 / 4096 rows as before (7.4 / 10.7 us), 8192 rows 18.7 -> 16.9 us,
@@ -1449,30 +1261,10 @@ hipError_t dispatch_area_full(const FwdArgs& a, hipStream_t s)
 // full-row forward serves, sharing its CDF builder.  The gradient walk keeps the canonical stable order (U before V on
 // ties): the gradient of a run of equal levels belongs to the run's last member.
 // ---------------------------------------------------------------------------------------------
-// 16-byte gradient store.  SOT_GRAD_STORE_SC1 = 1: write-through (`sc1`): the bytes leave the XCD's L2 while the kernel still computes,
-// instead of sitting there dirty until the end-of-kernel release writes all of them back (MI355X_MICROARCH.md, price list rows
-// "boundary": + B / 6 TB/s behind B dirty bytes, and "publish-large") -- the training form leaves 64 MB of gradients per launch.
-// MEASURED (round 3, 8192 x 2048, profiles/r3_walk_experiments_ab.txt): training form 78.6 us plain, 79.2 us sc1, 79.1 us sc0 sc1,
-// 77.8 us nt; both-gradient backward 91.1 -> 95.0 us with sc1.  The dirty lines are not what the call waits for; nt's 1 % is not
-// worth making the consumer of the gradient (the STFT backward kernel, the optimizer) fetch it from HBM.  Plain stores stay.
-#ifndef SOT_GRAD_STORE_SC1
-#define SOT_GRAD_STORE_SC1 0
-#endif
-typedef float v4f_t __attribute__((ext_vector_type(4)));
+// 16-byte gradient store: plain (write-through or non-temporal forms measured no faster, profiles/r3_walk_experiments_ab.txt)
 __device__ __forceinline__ void store_grad16(float* dst, float a, float b, float c, float d)
 {
-#if SOT_GRAD_STORE_SC1 == 1
-    const v4f_t v = {a, b, c, d};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(v) : "memory");
-#elif SOT_GRAD_STORE_SC1 == 2
-    const v4f_t v = {a, b, c, d};
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(dst), "v"(v) : "memory");
-#elif SOT_GRAD_STORE_SC1 == 3
-    const v4f_t v = {a, b, c, d};
-    asm volatile("global_store_dwordx4 %0, %1, off nt" : : "v"(dst), "v"(v) : "memory");
-#else
     *reinterpret_cast<float4*>(dst) = make_float4(a, b, c, d);
-#endif
 }
 
 __device__ __forceinline__ void lds_store(uint32_t addr, float v)
@@ -1490,12 +1282,7 @@ __device__ __forceinline__ void lds_store(uint32_t addr, float v)
 // address: one contiguous KiB per wave instruction, whole lines except the row's two ends (components outside the row are stored one
 // dword at a time by the one or two lanes that own the ragged chunks).  The stores are issued at the top of the NEXT row iteration
 // (after the barrier that closes this one): no extra barrier, and they overlap the next row's staging.
-#ifndef SOT_GRAD_STAGED
-#define SOT_GRAD_STAGED 1
-#endif
-#ifndef SOT_GRAD_STAGED_MIN_BINS
-#define SOT_GRAD_STAGED_MIN_BINS 1025
-#endif
+constexpr int kGradStagedMinBins = 1025;
 template <int G, int N>
 __device__ __forceinline__ void flush_row_grad(const float* lds_row, float* grow, int t)
 {
@@ -1572,13 +1359,12 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
     // FETCH x 2 + WRITE 250.2 -> 204.3 MB (1.241 -> 1.014 x algorithmic), both-gradient backward 123.2 -> 103.0 us (1.010 x), 4096 x 1025
     // 28.8 -> 27.6 us, 4096 x 2049 52.5 -> 50.6 us; 8192 x 513 24.8 vs 24.9; one-wave rows lose (16384 x 257: 26.0 -> 26.6 us, traffic 1.023 x either
     // way; 32768 x 129: 33.1 -> 34.1 us): their CPT = 3 / 5 stores per thread already complete each line within a few instructions.
-    constexpr bool STAGE_OUT = (NX >= SOT_GRAD_STAGED_MIN_BINS) && (SOT_GRAD_STAGED != 0);
+    constexpr bool STAGE_OUT = NX >= kGradStagedMinBins;
     const bool stage_x = STAGE_OUT && WANT_X && b.gx != nullptr && c.x_ident;
     const bool stage_y = STAGE_OUT && b.gy != nullptr && c.y_ident;
     int64_t pend_row = -1;   // wave-uniform: the row whose gradients wait in this row group's LDS slots
     (void)stage_x; (void)stage_y;
 
-    stagger_barriers<ROWS, NW>(rg);
     for (; row0 < a.B; row0 += row_step) {
         const int64_t row = row0 + rg;
         const bool valid = row < a.B;
@@ -1606,7 +1392,7 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
         // ---- merge walk over (pad zero levels ++ U, V), exactly E steps per thread.  The gradient of a level is known one
         //      step later (it is non-zero only if the NEXT level starts a new run), so the store of element k-1 happens at
         //      step k; the thread's last element is closed by peeking at level D0+E.
-        __builtin_amdgcn_s_setprio(SOT_WALK_PRIO);
+        __builtin_amdgcn_s_setprio(kWalkPrio);
         float lacc = 0.0f, lq = 0.0f;   // WITH_LOSS: this thread's part of the row loss, the previous merged level
         if (GA == G || t < GA) {
             const uint32_t poff4 = 4u * (uint32_t)((ROWS - rg) * L.rowf);  // level -> its position (shared copy behind the rows)
@@ -1629,57 +1415,11 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
                 const float cst = transport_cost<PM>(c.PX[lower_rank(U, N, q0)], c.PY[lower_rank(V, N, q0)], a.p);
                 dcur = (LIM && q0 > 1.0f) ? 0.0f : cst;
             }
-#if SOT_BWD_LOSER
-            // The walk in the forward kernel's "loser" form -- (w, wp) the head fetched last, (r, rp) the head that lost the last
-            // comparison; only the consumed head's stream is read again, three selects per step instead of six -- WITH the canonical
-            // tie order the gradient needs (U before V on equal heads): which stream w belongs to is a lane mask (w_is_u) that
-            // flips whenever the loser changes, maintained and combined on the scalar unit.  `prevn` = address of the element
-            // consumed last + 4 (its gradient slot is an instruction immediate away).
-            float w = ua, wp = xa, r = vb, rp = yb;
-            bool w_is_u = true;
-            uint32_t pw = ou + 4u, pr = ov + 4u;
-            uint32_t prevn = uw32 + 4u * (uint32_t)(PAD + N) + 4u;   // U[N]'s gradient slot: a scratch target for "no element yet"
-#if SOT_FULL_WALK_UNROLL > 0
-#pragma unroll SOT_FULL_WALK_UNROLL
-#endif
-            for (int s2 = 0; s2 < E; ++s2) {
-                const bool tu = (w < r) || ((w == r) && w_is_u);   // consume w's head
-                const float q = tu ? w : r;
-                float cst = transport_cost<PM>(wp, rp, a.p);
-                if (LIM && q > 1.0f) cst = 0.0f;
-                if constexpr (WITH_LOSS) {
-                    lacc = fmaf(q - lq, cst, lacc);   // (the forward kernel zeroes the width instead of the cost: the same product, 0)
-                    lq = q;
-                }
-                const bool new_run = !(q == qprev);
-                if (!SLIM || slot) lds_store(prevn + (GOFF4 - 4u), new_run ? (dcur - cst) : 0.0f);
-                dcur = new_run ? cst : dcur;
-                qprev = q;
-                const uint32_t nx = tu ? pw : pr;    // next unread element of the consumed stream
-                pr = tu ? pr : pw;
-                pw = nx + 4u;
-                r = tu ? r : w;
-                rp = tu ? rp : wp;
-                w_is_u = (tu == w_is_u);             // unchanged when w's head was consumed, flipped when the loser changed
-                if constexpr (SLIM) slot = !w_is_u;  // the element consumed now is a V element <=> the stream being refilled is V's
-                prevn = nx;
-                w = lds_load(nx);
-                wp = lds_load(nx + poff4);
-            }
-            {   // close the last element with the level that follows this thread's range (0 cost past the end)
-                const float qn = fminf(w, r);
-                float cn = transport_cost<PM>(wp, rp, a.p);
-                if ((LIM && qn > 1.0f) || (t == GA - 1)) cn = 0.0f;
-                const bool new_run = !(qn == qprev) || (t == GA - 1);
-                if (!SLIM || slot) lds_store(prevn + (GOFF4 - 4u), new_run ? (dcur - cn) : 0.0f);
-            }
-#else
+            // (The forward kernel's loser form with the canonical tie order kept by a lane mask: no gain, profiles/r3_walk_experiments_ab.txt.)
             // LDS byte addresses of the next unread element of each stream, and of the element consumed last
             uint32_t pu = ou, pv = ov;
             uint32_t prev = uw32 + 4u * (uint32_t)(PAD + N);  // U[N]'s gradient slot: a scratch target for "no element yet"
-#if SOT_FULL_WALK_UNROLL > 0
 #pragma unroll SOT_FULL_WALK_UNROLL
-#endif
             for (int s2 = 0; s2 < E; ++s2) {
                 const bool tu = ua <= vb;
                 const float q = tu ? ua : vb;
@@ -1714,7 +1454,6 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
                 const bool new_run = !(qn == qprev) || (t == GA - 1);
                 if (!SLIM || slot) lds_store(prev + GOFF4, new_run ? (dcur - cn) : 0.0f);
             }
-#endif
         }
         __builtin_amdgcn_s_setprio(0);
         SOT_PH(sacc, 10);  // partition search + gradient walk
@@ -1855,7 +1594,7 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
 #pragma unroll
                     for (int k = 0; k < CPT; k += 4)
                         store_grad16(dst + e0 + k, ox[k], ox[k + 1], ox[k + 2], ox[k + 3]);
-                } else if (SOT_ROW_BUFFERS && Geo::RT && c.x_ident) {   // run-time lengths: stores past the row are dropped by the buffer
+                } else if (Geo::RT && c.x_ident) {   // run-time lengths: stores past the row are dropped by the buffer
                     const RowBuffer rb = row_buffer(dst, nreal);
 #pragma unroll
                     for (int k = 0; k < CPT; ++k) row_buffer_store(rb, e0 + k, ox[k]);
@@ -1872,7 +1611,7 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
 #pragma unroll
                     for (int k = 0; k < CPT; k += 4)
                         store_grad16(dst + e0 + k, oy[k], oy[k + 1], oy[k + 2], oy[k + 3]);
-                } else if (SOT_ROW_BUFFERS && Geo::RT && c.y_ident) {
+                } else if (Geo::RT && c.y_ident) {
                     const RowBuffer rb = row_buffer(dst, nreal);
 #pragma unroll
                     for (int k = 0; k < CPT; ++k) row_buffer_store(rb, e0 + k, oy[k]);
@@ -1900,7 +1639,6 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
             if (stage_y) flush_row_grad<G, N>(GV, b.gy + pend_row * (int64_t)N, t);
         }
     }
-    stagger_barriers<ROWS, NW>(ROWS - 1 - rg);
     if constexpr (WITH_LOSS) {
         if (a.mt.counters != nullptr) batch_mean_tail<ROWS * G>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
     }
@@ -1923,11 +1661,9 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
 // workgroups per CU (128 VGPRs) measured (training form, p = 1, interleaved A/B): 16384 x 1025 72.6 -> 66.0 us, 4096 x 1025 23.4 -> 22.1 us,
 // 4096 x 2049 42.1 -> 37.1 us (the merge backward: 77 / 27 / 45 us).  Skipping the gradient stores altogether changes nothing (73.1 vs
 // 73.1 us): the kernel is bound by occupancy and issue, not by its unaligned dword stores.
-#ifndef SOT_AT_MINB
-#define SOT_AT_MINB 4
-#endif
+constexpr int kAreaTrainMinWaves = 4;
 template <int G, int CPT, int ROWS, bool SQ, int NX = 0>
-__global__ __launch_bounds__(ROWS * G, (NX > 0 && CPT >= 9) ? SOT_AT_MINB : 1) void sot_area_train_kernel(const BwdArgs b)
+__global__ __launch_bounds__(ROWS * G, (NX > 0 && CPT >= 9) ? kAreaTrainMinWaves : 1) void sot_area_train_kernel(const BwdArgs b)
 {
     using Geo = FullGeo<G, CPT, ROWS, false, NX>;
     constexpr FullLayout L = Geo::L;
@@ -1976,7 +1712,7 @@ __global__ __launch_bounds__(ROWS * G, (NX > 0 && CPT >= 9) ? SOT_AT_MINB : 1) v
         const int64_t rn = min(row0 + row_step + rg, a.B - 1);
         float wx[CPT], wy[CPT], cu[CPT], cv[CPT];
         float Sx, Sy;
-        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, (SOT_AREA_LATE_FETCH != 0), true>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, true>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
                                                             more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv);
         float acc = 0.0f;
         double gb[CPT];      // the thread's own suffix sums (as floats they save no register: the peak is inside full_build_cdfs)
@@ -2041,10 +1777,6 @@ __global__ __launch_bounds__(ROWS * G, (NX > 0 && CPT >= 9) ? SOT_AT_MINB : 1) v
                 oy[k] = (float)(h * gr);
             }
             float* dst = b.gy + row * (int64_t)N;
-#ifdef SOT_AT_NOSTORE   /* diagnostic: no gradient leaves the kernel (one lane keeps the arithmetic alive) */
-            if (oy[0] == 123.456f) dst[e0] = oy[CPT - 1];
-            else
-#endif
             if (Geo::ALIGNED && c.y_ident) {
 #pragma unroll
                 for (int k = 0; k < CPT; k += 4) store_grad16(dst + e0 + k, oy[k], oy[k + 1], oy[k + 2], oy[k + 3]);
@@ -2070,7 +1802,7 @@ static hipError_t launch_area_train(const BwdArgs& b, hipStream_t s)
     static GridCache cache;
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
     const int64_t want = (b.f.B + ROWS - 1) / ROWS;
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();
     launch_maybe_profiled(kern, grid, block, lds, s, b);
     return hipGetLastError();
@@ -2107,13 +1839,12 @@ static hipError_t launch_forward_full(const FwdArgs& a, hipStream_t s)
 {
     auto kern = sot_forward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, RP>;
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
-    static const size_t extra_lds = debug_extra_lds();
-    const size_t lds = sizeof(float) * (size_t)L.total + extra_lds;
+    const size_t lds = sizeof(float) * (size_t)L.total;
     constexpr int block = ROWS * G;
     static GridCache cache;  // per instantiation, per device (sot_hip.hip: cached_resident_grid)
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
     const int64_t want = (a.B + ROWS - 1) / ROWS;
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();
     launch_maybe_profiled(kern, grid, block, lds, s, a);
     return hipGetLastError();
@@ -2189,7 +1920,7 @@ hipError_t dispatch_forward_full_rt(int pm, const FwdArgs& a, hipStream_t s)
         case 256: return dispatch_forward_full_g<64, 4, 4, -1>(pm, a, s);
         case 512: return dispatch_forward_full_g<64, 8, 4, -1>(pm, a, s);
         case 1024:   // large batches: one wave per row (16384 x 1000 paper mode 54.9 -> 50.6 us, 8192 rows 30.4 -> 29.9, 4096 rows 17.5 -> 19.2)
-            if (SOT_RT_1024_ONEWAVE_ROWS > 0 && a.B >= SOT_RT_1024_ONEWAVE_ROWS) return dispatch_forward_full_g<64, 16, 4, -1>(pm, a, s);
+            if (a.B >= kRt1024OneWaveRows) return dispatch_forward_full_g<64, 16, 4, -1>(pm, a, s);
             return dispatch_forward_full_g<128, 8, 2, -1>(pm, a, s);
         case 1536: return dispatch_forward_full_g<192, 8, 1, -1>(pm, a, s);
         case 2048:   // (two waves per row, 16 elements per thread: 53.6 vs 53.9 us at 8192 x 2000 -- nothing; one row per workgroup 64.3 us)
@@ -2227,9 +1958,8 @@ int full_rt_capacity(int n)
 {
     if (n <= 128) return 0;    // tiny rows: the generic (64, 8) kernel wastes less
     for (int cap = 256; cap <= 8192; cap <<= 1) {
-#if SOT_RT_MID_CAPACITIES   /* 1536 = 192 x 8, 3072 = 384 x 8: rows just above a power of two do not pay for twice their length */
+        // 1536 = 192 x 8, 3072 = 384 x 8: rows just above a power of two do not pay for twice their length
         if (cap >= 2048 && cap <= 4096 && n <= cap - cap / 4) return cap - cap / 4;
-#endif
         if (n <= cap) return cap;
     }
     return 0;
@@ -2239,9 +1969,6 @@ int full_rt_capacity(int n)
 // one-sided spectra of n_fft 256 ... 4096: 129 / 257 / 513 / 1025 / 2049 bins (the paper uses 257 and 1025; any alignment).
 bool forward_full_supports(int n, bool aligned16)
 {
-#ifdef SOT_FORCE_RT   /* diagnostic: every length through the run-time-length kernels (isolates their overhead at n = 2048) */
-    (void)aligned16; if (n > 0) return false;
-#endif
     return ((n == 512 || n == 1024 || n == 2048 || n == 4096 || n == 8192) && aligned16) || n == 129 || n == 257 || n == 513 ||
            n == 1025 || n == 2049;
 }
@@ -2257,7 +1984,7 @@ static hipError_t launch_forward_half(const FwdArgs& a, hipStream_t s)
     static GridCache cache;
     const int64_t want = (a.B + ROWS - 1) / ROWS;
     (void)hipGetLastError();
-    launch_maybe_profiled(kern, balanced_grid(want, cached_resident_grid(cache, kern, block, lds)), block, lds, s, a);
+    launch_maybe_profiled(kern, persistent_grid(want, cached_resident_grid(cache, kern, block, lds)), block, lds, s, a);
     return hipGetLastError();
 }
 
@@ -2293,13 +2020,13 @@ hipError_t dispatch_forward_full(const LaunchCfg&, int pm, const FwdArgs& a, siz
         case 8192: return dispatch_forward_full_g<1024, 8, 1>(pm, a, s);
         case 129:   // large batches: two rows per wave (sot_forward_half_kernel).  Paper mode, interleaved A/B: 8192 rows 7.5 -> 6.9 us, 16384 rows 11.7 -> 10.4,
                     // 32768 rows 19.8 -> 16.0, 65536 rows 35.0 -> 28.0 us
-            if (SOT_FWD_HALF_WAVE && a.B >= 8192) return dispatch_forward_half<5, 8, 129>(pm, a, s);
+            if (a.B >= 8192) return dispatch_forward_half<5, 8, 129>(pm, a, s);
             return dispatch_forward_full_g<64, 3, 4, 129>(pm, a, s);
         case 2049: return dispatch_forward_full_g<256, 9, 1, 2049>(pm, a, s);
         case 257:   // the same from ~40 000 rows: 16384 rows 15.5 -> 16.8 us, 32768 rows 25.6 -> 26.4, 49152 rows 40.4 -> 37.4, 65536 rows 53.0 -> 47.8 us
                     // (each row region carries its own copy of the positions -- the walk addresses a level's position at a constant offset -- so
                     // LDS holds 32 rows = 16 waves per CU: fewer, longer-running waves than the one-wave kernel, which only pays once the launch is long)
-            if (SOT_FWD_HALF_WAVE && a.B >= 40960) return dispatch_forward_half<9, 8, 257>(pm, a, s);
+            if (a.B >= 40960) return dispatch_forward_half<9, 8, 257>(pm, a, s);
             return dispatch_forward_full_g<64, 5, 4, 257>(pm, a, s);
         case 513: return dispatch_forward_full_g<64, 9, 4, 513>(pm, a, s);
         case 1025:
@@ -2308,7 +2035,7 @@ hipError_t dispatch_forward_full(const LaunchCfg&, int pm, const FwdArgs& a, siz
             // 19.3, 8192 rows 25.6 -> 23.3, 12288 rows 35.3 -> 31.6, 16384 rows 45.1 -> 42.2 us.  (Its thread-local sums group the row
             // differently: row losses agree with the two-wave kernels' to ~1e-7, not bit for bit.  The training kernel in this
             // geometry needs 17-element gradient arrays in registers and is slower: 85 -> 107 us at 16384 rows.)
-            if (SOT_FWD_1025_ONEWAVE_ROWS > 0 && a.B >= SOT_FWD_1025_ONEWAVE_ROWS) return dispatch_forward_full_g<64, 17, 4, 1025>(pm, a, s);
+            if (a.B >= kFwd1025OneWaveRows) return dispatch_forward_full_g<64, 17, 4, 1025>(pm, a, s);
             return dispatch_forward_full_g<128, 9, 2, 1025>(pm, a, s);  // 256 threads per row: 64.6 instead of 54.4 us at 16384 rows (round 1)
         default: return hipErrorInvalidConfiguration;
     }
@@ -2330,7 +2057,7 @@ static hipError_t launch_backward_full_x(const BwdArgs& b, hipStream_t s)
     static GridCache cache;  // per instantiation, per device (sot_hip.hip: cached_resident_grid)
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
     const int64_t want = (b.f.B + ROWS - 1) / ROWS;
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();
     launch_maybe_profiled(kern, grid, block, lds, s, b);
     return hipGetLastError();
@@ -2400,15 +2127,8 @@ static hipError_t dispatch_backward_full_y(int pm, const BwdArgs& b, hipStream_t
 int full_rt_capacity(int n);
 // y-only (training) kernels in the layout without U gradient slots, as the compile-time kernels of 1024 / 2048 points, capped at 128
 // VGPRs (MINB 4) so that the smaller region does buy another resident workgroup.  Interleaved A/B against the full layout (bit-identical
-// results): 1024-point geometry 16384 x 1000 paper mode 106.1 -> 96.6 us -- adopted; 2048-point geometry (two rows per workgroup)
-// 8192 x 2000 paper mode 109.1 -> 111.6 us, p = 3 126.8 -> 128.4 us, 8192 x 1500 p = 1 110.3 -> 104.2 us (without the cap: 155 VGPRs, ONE
-// workgroup per CU, 165 us) -- the spills cost what the fourth row buys; stays in the full layout.
-#ifndef SOT_RT_SLIM_1024
-#define SOT_RT_SLIM_1024 1
-#endif
-#ifndef SOT_RT_SLIM_2048
-#define SOT_RT_SLIM_2048 0
-#endif
+// results): 1024-point geometry 16384 x 1000 paper mode 106.1 -> 96.6 us -- adopted; 2048-point geometry 8192 x 2000 paper mode
+// 109.1 -> 111.6 us -- the spills cost what the fourth row buys; stays in the full layout.
 // run-time row lengths (see full_rt_capacity): both-gradient and y-only (training form: also the row losses) kernels
 hipError_t dispatch_backward_full_rt(int pm, const BwdArgs& b, hipStream_t s)
 {
@@ -2416,12 +2136,10 @@ hipError_t dispatch_backward_full_rt(int pm, const BwdArgs& b, hipStream_t s)
         case 256: return dispatch_backward_full_g<64, 4, 4, -1>(pm, b, s);
         case 512: return dispatch_backward_full_g<64, 8, 4, -1>(pm, b, s);
         case 1024:
-            if (SOT_RT_SLIM_1024 && b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, -1, true, 4>(pm, b, s);
-            return dispatch_backward_full_g<128, 8, 2, -1, SOT_RT_SLIM_1024 ? 1 : 3>(pm, b, s);
+            if (b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, -1, true, 4>(pm, b, s);
+            return dispatch_backward_full_g<128, 8, 2, -1, 1>(pm, b, s);
         case 1536: return dispatch_backward_full_g<192, 8, 1, -1>(pm, b, s);
-        case 2048:
-            if (SOT_RT_SLIM_2048 && b.gx == nullptr) return dispatch_backward_full_y<256, 8, 2, -1, true, 4>(pm, b, s);
-            return dispatch_backward_full_g<256, 8, 1, -1, SOT_RT_SLIM_2048 ? 1 : 3>(pm, b, s);
+        case 2048: return dispatch_backward_full_g<256, 8, 1, -1>(pm, b, s);
         case 3072: return dispatch_backward_full_g<384, 8, 1, -1>(pm, b, s);
         case 4096: return dispatch_backward_full_g<512, 8, 1, -1>(pm, b, s);
         default: return hipErrorInvalidConfiguration;
@@ -2433,52 +2151,32 @@ hipError_t dispatch_backward_full_rt(int pm, const BwdArgs& b, hipStream_t s)
 // Rows per workgroup of the y-only (training) kernel for 2048-bin rows.  Without gradient slots for U two rows and the shared
 // position copy take 68.7 KB: two workgroups = four rows per CU instead of three (one row with U slots + positions: 50.9 KB).
 // Measured at 8192 x 2048, paper mode: 79.7 instead of 81.5 us.
-#ifndef SOT_TRAIN_1025_FOUR
-#define SOT_TRAIN_1025_FOUR 1
-#endif
-#ifndef SOT_TRAIN_SLIM_MORE
-#define SOT_TRAIN_SLIM_MORE 1   /* 1024- and 2049-bin rows: the layout without U gradient slots buys another resident workgroup */
-#endif
-#ifndef SOT_TRAIN_513_FOUR
-#define SOT_TRAIN_513_FOUR 1   /* the same for 513-bin rows (35.5 KB per four rows): 8192 rows 26.6 -> 25.0 us, 32768 rows 75.8 -> 74.5 us */
-#endif
-#ifndef SOT_TRAIN_ROWS_2048
-#define SOT_TRAIN_ROWS_2048 2
-#endif
-
 hipError_t dispatch_backward_full(const LaunchCfg&, int pm, const BwdArgs& b, hipStream_t s)
 {
     switch (b.f.n) {
         case 512: return dispatch_backward_full_g<64, 8, 4>(pm, b, s);   // (the slim layout adds a fourth workgroup per CU here too: 64.5 vs 65.0 us, nothing)
         case 1024:   // y-only: 34.8 instead of 43.3 KB per two rows = eight rows per CU instead of six: 16384 rows 78.8 -> 73.4 us, 4096 rows 27.3 -> 26.0 us
-            if (SOT_TRAIN_SLIM_MORE && b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, 0, true, 1>(pm, b, s);
-            return dispatch_backward_full_g<128, 8, 2, 0, SOT_TRAIN_SLIM_MORE ? 1 : 3>(pm, b, s);
+            if (b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, 0, true, 1>(pm, b, s);
+            return dispatch_backward_full_g<128, 8, 2, 0, 1>(pm, b, s);
         case 2048:
-            if (SOT_TRAIN_ROWS_2048 == 2 && b.gx == nullptr) return dispatch_backward_full_y<256, 8, 2>(pm, b, s);
-            return dispatch_backward_full_g<256, 8, 1, 0, SOT_TRAIN_ROWS_2048 == 2 ? 1 : 3>(pm, b, s);
+            if (b.gx == nullptr) return dispatch_backward_full_y<256, 8, 2>(pm, b, s);
+            return dispatch_backward_full_g<256, 8, 1, 0, 1>(pm, b, s);
         case 4096: return dispatch_backward_full_g<512, 8, 1>(pm, b, s);
         case 129: return dispatch_backward_full_g<64, 3, 4, 129>(pm, b, s);
         case 2049:   // y-only: 47.7 instead of 57 KB per row = three rows per CU instead of two: 8192 rows 119.2 -> 95.5 us
-            if (SOT_TRAIN_SLIM_MORE && b.gx == nullptr) return dispatch_backward_full_y<256, 9, 1, 2049, true, 1>(pm, b, s);
-            return dispatch_backward_full_g<256, 9, 1, 2049, SOT_TRAIN_SLIM_MORE ? 1 : 3>(pm, b, s);
+            if (b.gx == nullptr) return dispatch_backward_full_y<256, 9, 1, 2049, true, 1>(pm, b, s);
+            return dispatch_backward_full_g<256, 9, 1, 2049, 1>(pm, b, s);
         case 257:
-#if defined(SOT_TRAIN_257_SIX)   /* diagnostic: 1 = full layout, 2 = without U gradient slots; both compiled for six waves per SIMD.
-                                    Training form: 16384 rows 26.2 -> 25.2 us either way, 65536 rows 80.8 -> 82.4 / 82.9 us: not adopted */
-            if (b.gx == nullptr) return dispatch_backward_full_y<64, 5, 4, 257, (SOT_TRAIN_257_SIX == 2), 6>(pm, b, s);
-#endif
             return dispatch_backward_full_g<64, 5, 4, 257>(pm, b, s);
         case 513:
-            if (SOT_TRAIN_513_FOUR && b.gx == nullptr) return dispatch_backward_full_y<64, 9, 4, 513, true, 4>(pm, b, s);
-            return dispatch_backward_full_g<64, 9, 4, 513, SOT_TRAIN_513_FOUR ? 1 : 3>(pm, b, s);
+            // y-only: the layout without U gradient slots (35.5 KB per four rows): 8192 rows 26.6 -> 25.0 us, 32768 rows 75.8 -> 74.5 us
+            if (b.gx == nullptr) return dispatch_backward_full_y<64, 9, 4, 513, true, 4>(pm, b, s);
+            return dispatch_backward_full_g<64, 9, 4, 513, 1>(pm, b, s);
         case 1025:
             // y-only (training) kernel: the layout without U gradient slots (39 KB per two rows) compiled for four workgroups per CU
             // (128 VGPRs, 9 dwords spilled) holds eight rows per CU instead of six: 4096 rows 30.8 -> 29.1 us, 16384 rows 88.9 -> 85.6 us
-            if (SOT_TRAIN_1025_FOUR && b.gx == nullptr) return dispatch_backward_full_y<128, 9, 2, 1025, true, 4>(pm, b, s);
-#ifdef SOT_WIDE_1025_ROWS   /* diagnostic: batches of at most this many rows run 256 threads x 5 elements per row.  Training form,
-                               paper mode: 2048 rows 20.0 vs 21.2 us, 4096 rows 32.7 vs 31.0, 8192 rows 56.6 vs 50.4, 16384 rows 103.4 vs 89.3 */
-            if (b.gx == nullptr && b.f.B <= SOT_WIDE_1025_ROWS) return dispatch_backward_full_y<256, 5, 1, 1025, false>(pm, b, s);
-#endif
-            return dispatch_backward_full_g<128, 9, 2, 1025, SOT_TRAIN_1025_FOUR ? 1 : 3>(pm, b, s);
+            if (b.gx == nullptr) return dispatch_backward_full_y<128, 9, 2, 1025, true, 4>(pm, b, s);
+            return dispatch_backward_full_g<128, 9, 2, 1025, 1>(pm, b, s);
         default: return hipErrorInvalidConfiguration;
     }
 }

@@ -31,29 +31,11 @@
 #ifndef SOT_PART
 #define SOT_PART 4095
 #endif
-// Timing-only ablation builds (tools/ablate.py; results are WRONG on purpose): bit 0 no merge walk, bit 1 no partition
-// search, bit 2 no row mass, bit 3 no division, bit 4 no CDF scan.  Never defined in the product build.
-#ifndef SOT_WAVE_SORT
-#define SOT_WAVE_SORT 1   /* 0: the in-LDS merge sort of round 4 everywhere (A/B switch) */
-#endif
-#ifndef SOT_ABLATE
-#define SOT_ABLATE 0
-#endif
 // Waves inside the partition search + merge walk (dependent LDS chains) run at raised priority so that they win issue
 // slots over co-resident waves in throughput phases: measured -2.7 % kernel time (interleaved A/B, steady state).
-#ifndef SOT_WALK_PRIO
-#define SOT_WALK_PRIO 1
-#endif
-#ifndef SOT_MASS_PRIO
-#define SOT_MASS_PRIO 2
-#endif
-// tuning knobs of the A/B harness (tools/ab_probe.py); the defaults are the measured best
-#ifndef SOT_E_MODE
-#define SOT_E_MODE 0   /* 0: ceil(K/G) forced odd (58.45 us with walk unroll 2); 1: plain (59.2); 2: even with odd half */
-#endif
-#ifndef SOT_WALK_UNROLL
-#define SOT_WALK_UNROLL 2  /* 0: compiler's choice (x4): 59.45 us; 1: 59.95; 2: 58.85 */
-#endif
+constexpr int kWalkPrio = 1;
+constexpr int kMassPrio = 2;
+#define SOT_WALK_UNROLL 2  /* merge walk unroll (a #pragma needs the literal): 58.85 us against 59.45 for the compiler's x4 */
 
 namespace sot {
 
@@ -81,8 +63,6 @@ __host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
 __host__ __device__ constexpr int merge_steps(int K, int G)
 {
     const int e = (K + G - 1) / G;
-    if (SOT_E_MODE == 1) return e;
-    if (SOT_E_MODE == 2) return ((e + 1) & ~3) + 2;  // E/2 odd: 2, 6, 10, 14, 18, ...
     return e | 1;
 }
 
@@ -440,7 +420,7 @@ __device__ __forceinline__ void build_cdfs(const FwdArgs& a, const RowCtx<G>& c,
     //      staged row is still in its original column order here) -----------------------------------
     float Sx = 1.0f, Sy = 1.0f;  // prenormalised: w / 1.0f == w exactly, weights enter the CDF unchanged
     float rSx = 1.0f, rSy = 1.0f;  // reciprocals of the guarded masses (computed once per row by the fold waves)
-    if (!(SOT_ABLATE & 4) && !c.prenorm) {
+    if (!c.prenorm) {
         if (sq) {
             mass_chunk_sums<G, true>(U, c.partx, c.mpx, t);
             if (!c.dn) mass_chunk_sums<G, true>(V, c.party, c.mpy, (t + G / 2) & (G - 1));
@@ -454,7 +434,7 @@ __device__ __forceinline__ void build_cdfs(const FwdArgs& a, const RowCtx<G>& c,
         // in its two half-waves): the 32 column totals are exchanged through this wave's own LDS slots.
         // (Doing this redundantly in every wave to save the barrier below was measured 10 % SLOWER.)
         float* const Sv = c.red + NW;
-        __builtin_amdgcn_s_setprio(SOT_MASS_PRIO);
+        __builtin_amdgcn_s_setprio(kMassPrio);
         if (NW >= 2) {
             if (c.wv < 2 && !(c.wv == 1 && c.dn)) {
                 const float* raw = c.wv ? V : U;
@@ -540,7 +520,6 @@ __device__ __forceinline__ void build_cdfs(const FwdArgs& a, const RowCtx<G>& c,
         uint32_t risk = 0xFFFFFFFFu;
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
-            if (SOT_ABLATE & 8) { qx[k] = wx[k] * rx; qy[k] = wy[k] * ry; continue; }
             qx[k] = div_by_row_constant(sq ? wx[k] * wx[k] : wx[k], Sxh, rx, risk);
             qy[k] = div_by_row_constant(sq ? wy[k] * wy[k] : wy[k], Syh, ry, risk);
         }
@@ -565,8 +544,8 @@ __device__ __forceinline__ void build_cdfs(const FwdArgs& a, const RowCtx<G>& c,
             py[k] = runy;
         }
     }
-    const double inx = (SOT_ABLATE & 16) ? runx : wave_incl_scan(runx), iny = (SOT_ABLATE & 16) ? runy : wave_incl_scan(runy);
-    double exx = (SOT_ABLATE & 16) ? 0.0 : wave_shift_right1(inx), exy = (SOT_ABLATE & 16) ? 0.0 : wave_shift_right1(iny);
+    const double inx = wave_incl_scan(runx), iny = wave_incl_scan(runy);
+    double exx = wave_shift_right1(inx), exy = wave_shift_right1(iny);
     if (NW > 1 && c.lane == kWave - 1) { c.wtot[c.wv] = inx; c.wtot[NW + c.wv] = iny; }
     SOT_STAMP(4);
     row_sync<G / kWave>();  // every raw weight has been read (also through permutations) before U/V are rewritten
@@ -623,19 +602,15 @@ __device__ __forceinline__ int lower_rank(const float* A, int len, float q)
 // Register cap (waves per SIMD) of the one-wave-per-row CSR kernel: 146 VGPRs = three waves per SIMD without it; compiled for four
 // (128 VGPRs) config 4's 8192 ragged rows take 30.8 instead of 33.0 us (five: 42.4, six: 56.5 -- spills).  The dense generic kernels
 // keep their registers: the same cap on 8192 x 1000 costs 46 -> 58 us (12 elements per thread spill).
-#ifndef SOT_CSR_MIN_WAVES
-#define SOT_CSR_MIN_WAVES 4
-#endif
+constexpr int kCsrMinWaves = 4;
 // Register cap of the per-row-position FORWARD kernels on 256-thread workgroups (the in-register block sort of merge_sort16_kv2 pushes them
-// to 168 ... 212 VGPRs = two waves per SIMD, i.e. two of the four workgroups the LDS would hold): SOT_ROWPOS_MIN_WAVES waves per SIMD (7 dwords
+// to 168 ... 212 VGPRs = two waves per SIMD, i.e. two of the four workgroups the LDS would hold): kRowposMinWaves waves per SIMD (7 dwords
 // spilled).  Measured 4096 x 2048 paper mode: unsorted rows 246 -> 192 us, sorted rows 77 -> 63 us (one sort block per thread + the cap).
-#ifndef SOT_ROWPOS_MIN_WAVES
-#define SOT_ROWPOS_MIN_WAVES 3
-#endif
+constexpr int kRowposMinWaves = 3;
 // (The generic shared-position kernels of the 2048-point geometry also sit just above a register step in some instantiations -- forward 129 ... 140
 // VGPRs, backward 176 -- but holding them to the step changes nothing: forward 52.8 vs 52.8 us, both-gradient backward 120.1 vs 119.7 us at 8192 x 2048.)
 template <int G, int CPT, bool ROWPOS, bool QUANT, int PM, bool LIM, bool VEC, bool CSR = false, int SQM = 2>
-__global__ __launch_bounds__((G < 256 ? 256 : G), ((CSR && G == 64) ? SOT_CSR_MIN_WAVES : (ROWPOS && !CSR && G <= 256 && CPT == 8) ? SOT_ROWPOS_MIN_WAVES : 1)) void sot_forward_kernel(const FwdArgs a)
+__global__ __launch_bounds__((G < 256 ? 256 : G), ((CSR && G == 64) ? kCsrMinWaves : (ROWPOS && !CSR && G <= 256 && CPT == 8) ? kRowposMinWaves : 1)) void sot_forward_kernel(const FwdArgs a)
 {
     static_assert(!CSR || (ROWPOS && !VEC && !QUANT), "the CSR form has per-row positions and unaligned rows");
     constexpr int BLOCK = (G < 256 ? 256 : G);
@@ -715,7 +690,7 @@ __global__ __launch_bounds__((G < 256 ? 256 : G), ((CSR && G == 64) ? SOT_CSR_MI
         // ---- P4: merge of the two CDFs = sort(cat(U,V)) + searchsorted + take_along_dim -----------
         //      (losses.py:295-298), level widths, cutoff mask, |.|^p, weighted sum (:301-313)
         float acc = 0.0f;
-        __builtin_amdgcn_s_setprio(SOT_WALK_PRIO);
+        __builtin_amdgcn_s_setprio(kWalkPrio);
         if (t < c.Ga) {
             // Walk over (Uw, V) where Uw = pad zero levels ++ U: exactly E steps for every thread.
             const float* const Uw = U - c.pad;
@@ -723,8 +698,7 @@ __global__ __launch_bounds__((G < 256 ? 256 : G), ((CSR && G == 64) ? SOT_CSR_MI
             const int nw = n + c.pad;
             const int D0 = t * c.E;
             const uint32_t ub1 = lds_addr(Uw) - 4u;  // partition search on LDS byte addresses (merge_path_steps32)
-            const int i0 = (SOT_ABLATE & 2) ? min(D0 >> 1, nw)
-                                            : (int)((merge_path_steps32(ub1, lds_addr(V) + 4u * (uint32_t)D0 + ub1, nw, m, D0, c.topk) - ub1) >> 2);
+            const int i0 = (int)((merge_path_steps32(ub1, lds_addr(V) + 4u * (uint32_t)D0 + ub1, nw, m, D0, c.topk) - ub1) >> 2);
             SOT_STAMP(6);
             const int j0 = D0 - i0;
             float qprev = 0.0f;  // Q_0 := 0 (the pad of losses.py:301)
@@ -745,10 +719,8 @@ __global__ __launch_bounds__((G < 256 ? 256 : G), ((CSR && G == 64) ? SOT_CSR_MI
                 float w = ua, wp = xa, r = vb, rp = yb;
                 const uint32_t lb32 = lds_addr(lb);  // 32-bit LDS addresses: one VGPR per stream, no re-basing add per access
                 uint32_t pw = lb32 + 4u * (uint32_t)i0 + 4u, pr = lb32 + 4u * (uint32_t)(voff + j0) + 4u;
-#if SOT_WALK_UNROLL > 0
 #pragma unroll SOT_WALK_UNROLL
-#endif
-                for (int s = 0; s < ((SOT_ABLATE & 1) ? 1 : c.E); ++s) {
+                for (int s = 0; s < c.E; ++s) {
                     const bool cw = w <= r;
                     const float q = cw ? w : r;
                     const float cost = transport_cost<PM>(wp, rp, c.p);
@@ -765,10 +737,8 @@ __global__ __launch_bounds__((G < 256 ? 256 : G), ((CSR && G == 64) ? SOT_CSR_MI
                     wp = lds_load(nx + poff4);
                 }
             } else
-#if SOT_WALK_UNROLL > 0
 #pragma unroll SOT_WALK_UNROLL
-#endif
-            for (int s = 0; s < ((SOT_ABLATE & 1) ? 1 : c.E); ++s) {
+            for (int s = 0; s < c.E; ++s) {
                 const bool tu = ua <= vb;
                 const float q = tu ? ua : vb;
                 const float cost = transport_cost<PM>(xa, yb, c.p);
@@ -894,7 +864,7 @@ __global__ __launch_bounds__((G < 256 ? 256 : G)) void sot_backward_kernel(const
         // ---- merge walk over (pad zero levels ++ U, V), exactly E steps per thread.  The gradient of a level
         //      is known one step later (it is non-zero only if the NEXT level starts a new run), so the store
         //      of element k-1 happens at step k; the thread's last element is closed by peeking at level D0+E.
-        __builtin_amdgcn_s_setprio(SOT_WALK_PRIO);
+        __builtin_amdgcn_s_setprio(kWalkPrio);
         if (t < c.Ga) {
             const float* const Uw = U - c.pad;
             const float* const PXw = PX - c.pad;
@@ -1089,14 +1059,6 @@ static inline int device_cu_count()
     return n;
 }
 
-// Experiment knob (never set in production): SOT_DEBUG_EXTRA_LDS=<bytes> pads the dynamic LDS request of the
-// forward kernel to throttle its occupancy, which separates latency-bound from issue-bound behaviour.
-static inline size_t debug_extra_lds()
-{
-    const char* e = getenv("SOT_DEBUG_EXTRA_LDS");
-    return e ? (size_t)atol(e) : 0;
-}
-
 struct LaunchCfg { int G, CPT; };
 
 // Row-group geometries: (threads per row, contiguous elements per thread).  G*CPT >= max(n, m).
@@ -1141,19 +1103,11 @@ struct GridCache {
     struct Entry { size_t lds; int grid; bool attr; } e[kMaxDevices] = {};
 };
 
-// Grid of a persistent kernel whose workgroups stride over `want` row groups, at most `cap` of them resident.  SOT_BALANCED_GRID = 1
-// gives every workgroup the same number of row groups (ceil(want / rounds) workgroups) instead of `cap` workgroups of which some run
-// one round more.  Measured (8192 x 2048): merge-free and merge forward unchanged (30.0 / 45.4 us), training form 86.2 instead of
-// 81.5 us (745 instead of 768 workgroups leave some CUs with two resident workgroups instead of three for the whole launch): off.
-#ifndef SOT_BALANCED_GRID
-#define SOT_BALANCED_GRID 0
-#endif
-static inline int balanced_grid(int64_t want, int cap)
+// Grid of a persistent kernel whose workgroups stride over `want` row groups, at most `cap` of them resident (some run one
+// round more: splitting the rows evenly over fewer workgroups was measured 5 % slower for the training form).
+static inline int persistent_grid(int64_t want, int cap)
 {
-    if (want <= cap) return (int)want;
-    if (!SOT_BALANCED_GRID) return cap;
-    const int64_t rounds = (want + cap - 1) / cap;
-    return (int)((want + rounds - 1) / rounds);
+    return want <= cap ? (int)want : cap;
 }
 
 template <typename Kernel>
@@ -1272,7 +1226,7 @@ int run_position_grad(const sot_problem* pr, const float* grad_row, int64_t grad
 int run_column_sum(const float* rows, int64_t B, int n, int64_t stride, float* out, void* stream);
 
 #ifdef SOT_STUB_MISSING_PARTS
-// diagnostic single-file builds (stamps / ablation) compile a subset of the parts: resolve the rest with stubs
+// diagnostic single-file builds (e.g. stamps) compile a subset of the parts: resolve the rest with stubs
 #if !(SOT_PART & 1)
 template <> hipError_t dispatch_forward<false>(const LaunchCfg&, bool, int, bool, const FwdArgs&, size_t, int64_t, int, hipStream_t) { return hipErrorInvalidDeviceFunction; }
 #endif
@@ -1319,11 +1273,9 @@ template <int G, int CPT, bool ROWPOS, bool QUANT, int PM, bool LIM, bool VEC, i
 static hipError_t launch_forward(const FwdArgs& a, size_t lds, int64_t want, int block, hipStream_t s)
 {
     auto kern = sot_forward_kernel<G, CPT, ROWPOS, QUANT, PM, LIM, VEC, false, SQM>;
-    static const size_t extra_lds = debug_extra_lds();
-    lds += extra_lds;
     static GridCache cache;  // per instantiation (function-local static: thread-safe initialisation)
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, a);
     return hipGetLastError();
@@ -1433,7 +1385,7 @@ static hipError_t launch_backward(const BwdArgs& b, size_t lds, int64_t want, in
     auto kern = sot_backward_kernel<G, CPT, ROWPOS, PM, LIM, VEC>;
     static GridCache cache;  // per instantiation (function-local static: thread-safe initialisation)
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, b);
     return hipGetLastError();
@@ -1662,7 +1614,7 @@ static hipError_t launch_position_grad(const PosGradArgs& b, size_t lds, int64_t
     auto kern = sot_position_grad_kernel<G, CPT, ROWPOS>;
     static GridCache cache;
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, b);
     return hipGetLastError();
@@ -2012,16 +1964,12 @@ static __device__ __attribute__((noinline)) void wave_merge_sort_array(float* ke
     merge_sort16_kv2<MAXB>(job, none, lane, kWave, [] { row_sync<1>(); });
     row_sync<1>();
 }
-#ifndef SOT_ROWPOS_SORT_MAX_WG
-#define SOT_ROWPOS_SORT_MAX_WG 4
-#endif
-#ifndef SOT_ROWPOS_SORT_WAVES
-#define SOT_ROWPOS_SORT_WAVES 2   /* wavefronts per SIMD the pre-sort kernel is compiled for (LDS: 16.9 KB per wave of the 32-keys-per-lane form = 8 waves per CU) */
-#endif
+constexpr int kRowposSortMaxWg = 4;
+constexpr int kRowposSortWaves = 2;   // wavefronts per SIMD the pre-sort kernel is compiled for (LDS: 16.9 KB per wave of the 32-keys-per-lane form = 8 waves per CU)
 
 // VEC: n, m multiples of 4, position rows 16-byte aligned, permutation rows 8-byte aligned (16-byte loads, 8-byte stores); FULL: n == m == 64 KPL
 template <int KPL, bool FULL, bool VEC>
-__global__ __launch_bounds__(256, SOT_ROWPOS_SORT_WAVES) void sot_rowpos_sort_kernel(const float* __restrict__ xpos, const float* __restrict__ ypos, int64_t B, int n, int m,
+__global__ __launch_bounds__(256, kRowposSortWaves) void sot_rowpos_sort_kernel(const float* __restrict__ xpos, const float* __restrict__ ypos, int64_t B, int n, int m,
                                                                  int64_t xps, int64_t yps, uint16_t* __restrict__ perm)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -2078,7 +2026,7 @@ __global__ __launch_bounds__(256, SOT_ROWPOS_SORT_WAVES) void sot_rowpos_sort_ke
 #pragma unroll
                 for (int r = 0; r < KPL; ++r) si[r] = (uint32_t)wsort_elem<VEC>(r, lane);
             } else {
-                const bool done = wave_sort_core<KPL, false, FULL, VEC, false, true>(x, [src](uint32_t i) { return src[i]; }, nullptr, idx, len, lane, sk, si);
+                const bool done = wave_sort_core<KPL, false, FULL, VEC, false>(x, [src](uint32_t i) { return src[i]; }, nullptr, idx, len, lane, sk, si);
                 row_sync<1>();   // the scratch image is free again
                 if (!done) {     // declined (clustered / non-finite positions; wave-uniform): the stable merge sort of round 4, by this wavefront alone
                     constexpr int NP = 64 * KPL;
@@ -2115,11 +2063,11 @@ int launch_rowpos_sort(const float* xpos, const float* ypos, int64_t B, int n, i
                          (reinterpret_cast<uintptr_t>(dest) & 7) == 0 && (n & 3) == 0 && (m & 3) == 0;
     (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
     auto go = [&](auto kern, int kpl) {
-        const size_t lds = (size_t)(sot::align4(sot::imax(sot::sort16_capacity(sot::sort16_npad(64 * kpl)), wave_sort_scratch(kpl, true))) + sot::align4(sot::sort16_capacity(sot::sort16_npad(64 * kpl)))) * 4 * 4;   // 4 waves x (idx / scratch | key)
+        const size_t lds = (size_t)(sot::align4(sot::imax(sot::sort16_capacity(sot::sort16_npad(64 * kpl)), wave_sort_scratch(kpl))) + sot::align4(sot::sort16_capacity(sot::sort16_npad(64 * kpl)))) * 4 * 4;   // 4 waves x (idx / scratch | key)
         static GridCache cache;   // (one per lambda instantiation, i.e. per kernel)
         allow_full_lds_once(cache, reinterpret_cast<const void*>(kern));
         int per_cu = (int)(kLdsLimit / lds);
-        if (per_cu > SOT_ROWPOS_SORT_MAX_WG) per_cu = SOT_ROWPOS_SORT_MAX_WG;   // four-wave workgroups: one wave of each per SIMD, at most 16 waves per CU
+        if (per_cu > kRowposSortMaxWg) per_cu = kRowposSortMaxWg;   // four-wave workgroups: one wave of each per SIMD, at most 16 waves per CU
         const int64_t groups = (2 * B + 3) / 4, cap = (int64_t)device_cu_count() * per_cu;   // one wave per array
         hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap)), dim3(256), lds, s, xpos, ypos, B, n, m, xps, yps, dest);
     };
@@ -2176,7 +2124,7 @@ int setup_launch(const sot_problem* pr, bool with_grad, void* workspace, size_t 
     // per-row positions nobody has sorted yet: the wave-sort kernel runs first (round 6) and the row kernel gathers through its
     // permutations -- into the caller's row_perm_out, else into the workspace when it is large enough (sot_workspace_bytes), else the
     // row kernel sorts in LDS as before
-    if (SOT_WAVE_SORT && l.rowpos && (pr->flags & SOT_FLAG_REQUIRE_SORT) && a.perm_in == nullptr && pr->B > 0 && n >= 2 && m >= 2 && n <= 2048 &&
+    if (l.rowpos && (pr->flags & SOT_FLAG_REQUIRE_SORT) && a.perm_in == nullptr && pr->B > 0 && n >= 2 && m >= 2 && n <= 2048 &&
         m <= 2048 && !(pr->flags & SOT_FLAG_NO_SPECIALIZE)) {
         uint16_t* dest = pr->row_perm_out;
         if (dest == nullptr && workspace != nullptr && workspace_bytes >= rowpos_perm_bytes(pr->B, n, m)) dest = reinterpret_cast<uint16_t*>(workspace);
@@ -2315,7 +2263,7 @@ static hipError_t launch_forward_csr(const FwdArgs& a, size_t lds, int64_t want,
     auto kern = sot_forward_kernel<G, CPT, true, false, PM, LIM, false, true>;
     static GridCache cache;  // per instantiation (function-local static: thread-safe initialisation)
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = balanced_grid(want, grid_cap);
+    const int grid = persistent_grid(want, grid_cap);
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, a);
     return hipGetLastError();
@@ -2572,7 +2520,7 @@ int sot_segmented_sort(const float* keys, int64_t B, int32_t n, int64_t row_stri
     if (B < 0 || n < 1 || row_stride < n) return SOT_ERR_BAD_SHAPE;
     if (B == 0) return SOT_OK;
     if (keys == nullptr) return SOT_ERR_NULL_POINTER;
-    if (SOT_WAVE_SORT && n <= 2048) {   // one wavefront per row (round 6)
+    if (n <= 2048) {   // one wavefront per row (round 6)
         hipStream_t st = reinterpret_cast<hipStream_t>(stream);
         if (n <= 128) return sot::launch_segmented_sort_wave<2>(keys, B, (int)n, row_stride, sorted_keys, indices, st);
         if (n <= 512) return sot::launch_segmented_sort_wave<8>(keys, B, (int)n, row_stride, sorted_keys, indices, st);

@@ -43,9 +43,7 @@ __device__ unsigned long long g_mss_stamps[64 * 16];
 #else
 #define MSS_STAMP(i) do { } while (0)
 #endif
-#ifndef MSS_WAVES_PER_EU
-#define MSS_WAVES_PER_EU 4   /* two 512-thread workgroups per CU (LDS: 2 x 80 KB): 128 VGPRs */
-#endif
+constexpr int kWavesPerEu = 4;   // two 512-thread workgroups per CU (LDS: 2 x 80 KB): 128 VGPRs
 
 // ---------------------------------------------------------------------------------------------
 struct MssArgs {
@@ -336,7 +334,7 @@ __device__ __forceinline__ void wave_task(const MssArgs& a, int s, int task, con
 // every scale); after that barrier its waves (4 or 16) are on their own, each with a CONTIGUOUS range of tasks -- mostly one scale, so the
 // scale's code stays in the instruction cache.
 template <bool GRAD, int KIND, int kWaves>
-__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(MSS_WAVES_PER_EU, MSS_WAVES_PER_EU))) void mss_fused_kernel(const MssArgs a)
+__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(kWavesPerEu, kWavesPerEu))) void mss_fused_kernel(const MssArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     v2f* const tw = reinterpret_cast<v2f*>(smem_f);      // tables first: every lane-part address into a wave's buffer stays positive
@@ -355,9 +353,6 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(MSS
     int s = 0;
     for (int task = (int)blockIdx.x * kWaves + wave; task < total; task += stride) {
         while (s + 1 < a.n_scales && task >= a.task_base[s + 1]) ++s;
-#ifdef MSS_ONLY_M      /* diagnostic builds: one transform size (compile time, register pressure of one body) */
-        wave_task<MSS_ONLY_M, GRAD, KIND>(a, s, task, tw, wn, zl);
-#else
         switch (a.logm[s]) {
             case 5: wave_task<5, GRAD, KIND>(a, s, task, tw, wn, zl); break;
             case 6: wave_task<6, GRAD, KIND>(a, s, task, tw, wn, zl); break;
@@ -366,15 +361,11 @@ __global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(MSS
             case 9: wave_task<9, GRAD, KIND>(a, s, task, tw, wn, zl); break;
             default: wave_task<10, GRAD, KIND>(a, s, task, tw, wn, zl); break;
         }
-#endif
     }
 }
 
 // Finish: the first workgroup turns the partial sums into the loss (per scale: fixed-order sum, mean as float32, `loss += mean` in the
 // reference's scale order, losses.py:411-424); every workgroup sums the wave spans covering its samples, scales and waves in order.
-#ifndef MSS_DIAG_NO_LOSS
-#define MSS_DIAG_NO_LOSS 0     /* diagnostic (timing only): the finish kernel without its loss reduction */
-#endif
 constexpr int kFinishThreads = 256;
 constexpr int kLossLoads = 4;       // partial sums per thread, scale and pass of the loss workgroup (8: one pass for 256 clips, but 148 VGPRs for the whole kernel -- three workgroups per CU instead of four: 12.7 -> 14.2 us)
 __global__ __launch_bounds__(kFinishThreads) void mss_finish_kernel(const MssArgs a)
@@ -390,7 +381,7 @@ __global__ __launch_bounds__(kFinishThreads) void mss_finish_kernel(const MssArg
             }
             a.loss[o] = total * a.post_scale;
         }
-    } else if (blockIdx.x == 0 && !MSS_DIAG_NO_LOSS) {      // (the FIRST workgroup: it is resident from the start, so the reduction runs beside the other workgroups' gathers, not behind them)
+    } else if (blockIdx.x == 0) {      // (the FIRST workgroup: it is resident from the start, so the reduction runs beside the other workgroups' gathers, not behind them)
         // all clips: per scale a fixed-order sum of the task partials -- thread t adds partials t, t + 256, ... of every scale, the waves reduce by
         // shuffles, thread 0 adds the four wave sums per scale in order.  The loads of ALL scales of a pass (kLossLoads per thread and scale) are issued
         // before the first is used (a loop that waits per load: 48 serialised round trips for 256 clips).
@@ -607,9 +598,7 @@ int sot_mss_loss_and_grad(const float* target, int64_t target_row_stride, const 
     }
     // persistent grid: at most 16 waves per CU; wave g takes tasks g, g + (waves of the grid), ...
     const int waves_needed = tasks < slots ? tasks : slots;
-#ifndef MSS_SKIP_FUSED     /* diagnostic (timing only, results are garbage): the finish kernel on its own */
     hipLaunchKernelGGL(kern, dim3((unsigned)((waves_needed + wg_waves - 1) / wg_waves)), dim3(64 * wg_waves), lds_bytes(wg_waves), st, a);
-#endif
     if (hipGetLastError() != hipSuccess) return SOT_ERR_LAUNCH;
     const int64_t work = a.want_grad ? (batch * ((((samples + 1) / 2) + 255) / 256) + 1) / 2 : 1;      // one workgroup per TWO (clip, 256 packed points) blocks
     const int64_t blocks = (work < 16384 ? (work < 1 ? 1 : work) : 16384) + ((a.want_grad && !per_clip) ? 1 : 0);      // + the loss workgroup

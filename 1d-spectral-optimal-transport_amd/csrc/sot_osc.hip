@@ -26,9 +26,7 @@ namespace sot_osc {
 constexpr int kThreads = 256;
 constexpr int kRun = 8;                       // consecutive samples per work item
 constexpr int kTileElems = 4096;              // most floats per envelope tile (S * sinusoids)
-#ifndef SOT_OSC_TILE
-#define SOT_OSC_TILE 2048                     /* preferred floats per envelope tile, see pick_segment */
-#endif
+constexpr int kPreferredTile = 2048;          // preferred floats per envelope tile, see pick_segment
 constexpr int kMaxSinusoids = kTileElems / kRun;
 constexpr int64_t kMaxSamples = 1 << 20;
 constexpr float kTwoPi = 6.283185307179586f;  // float32(2 * np.pi), as `frequency_envelopes * (2.0 * np.pi)` rounds it
@@ -412,7 +410,7 @@ inline int pick_segment(int64_t batch, int64_t samples, int K)
     while (S > kRun && (int64_t)S * K > kTileElems) S >>= 1;
     // preferred tile: 2048 floats per envelope (18 KB of LDS forward, 25 KB backward: 8 / 6 resident workgroups per CU instead of 4 / 3).
     // 256 clips x 4096 samples x 8 partials (tools/ab_synth.py): forward 64.5 -> 57.3 us, backward 79.2 -> 66.8 us; 1024: 65.7 / 79.6 us
-    while (S > 64 && (int64_t)S * K > SOT_OSC_TILE) S >>= 1;
+    while (S > 64 && (int64_t)S * K > kPreferredTile) S >>= 1;
     while (S > 64 && (int64_t)(S / kRun) * K >= 2 * kThreads && batch * ((samples + S - 1) / S) < 2048) S >>= 1;
     return S;
 }

@@ -29,34 +29,14 @@
 namespace sot_stft {
 
 constexpr int kThreads = 256;
-#ifndef SOT_STFT_FRAMES_PER_GROUP
-#define SOT_STFT_FRAMES_PER_GROUP 2
-#endif
-constexpr int kFramesPerGroup = SOT_STFT_FRAMES_PER_GROUP;  // backward: one frame slot per group of consecutive frames of a clip
+constexpr int kFramesPerGroup = 2;  // backward: one frame slot per group of consecutive frames of a clip
 constexpr int kMaxFft = 4096;
 
 #include "sot_stft_tables.inc"      // kPassTw, kWn (csrc/gen/make_stft_tables.py)
 
-#ifndef SOT_STFT_RAW_SQRT
-#define SOT_STFT_RAW_SQRT 0   /* 1: v_sqrt_f32 alone -- 14 % fewer VALU instructions, the same 24.7 us, and past the 2e-6 pin against float64 */
-#endif
-#ifndef SOT_STFT_PERSISTENT_WAVES
-#define SOT_STFT_PERSISTENT_WAVES 6   /* waves per SIMD the persistent forward kernel is compiled for: 6 = 76 VGPRs, no spills; 8 =
-                                         64 VGPRs with 10 spilled, measured slower (26.4 vs 21.9 us) */
-#endif
-#ifndef SOT_STFT_WAVE_FRAMES
-#define SOT_STFT_WAVE_FRAMES 1
-#endif
-// Timing-only ablation (tools/fusion_probe.py; results are WRONG on purpose, never defined in the product build): the forward kernels
-// compute every magnitude but store none -- what a consumer fused behind the transform would save on the producer's side.
-#ifndef SOT_STFT_ABLATE_STORE
-#define SOT_STFT_ABLATE_STORE 0
-#endif
-__device__ __forceinline__ void store_mag(float* dst, int k, float v)
-{
-    if (SOT_STFT_ABLATE_STORE) { if (v == 12345.678f) dst[k] = v; }   // keeps the value alive, never true for |.| / sqrt(n) of audio
-    else dst[k] = v;
-}
+// waves per SIMD the persistent forward kernel is compiled for: 6 = 76 VGPRs, no spills; 8 = 64 VGPRs with 10 spilled, measured
+// slower (26.4 vs 21.9 us)
+constexpr int kPersistentWaves = 6;
 
 // synchronisation of one frame slot (see Geo::wave_sync): the LDS executes a wavefront's instructions in issue order
 template <bool WAVE>
@@ -84,51 +64,32 @@ __device__ __forceinline__ void store_spec(float2* sp, int k, int mk, v2f xk, v2
 // instead of three).  Same three roundings as the vector expression, so every result is bit-identical to rounds 2-3.  (A fused form --
 // v_pk_mul + v_pk_fma, two instructions -- was measured too: its last-bit differences move rows of the SOT stage across the cutoff's
 // knife edge, which the float64 yardstick test of the audio-in chain does not tolerate: 1.2e-5 -> 1.5e-4 of the gradient's peak.)
-#ifndef SOT_STFT_ASM_CMUL
-#define SOT_STFT_ASM_CMUL 1
-#endif
 __device__ __forceinline__ v2f cmul(v2f a, v2f b)
 {
-#if SOT_STFT_ASM_CMUL
     v2f t;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(t) : "v"(a), "v"(b));   // (-a.y b.y, a.y b.x)
     return a.xx * b + t;
-#else
-    return a.xx * b + a.yy * (v2f){-b.y, b.x};
-#endif
 }
 // a * conj(b) = a.xx * (b.x, -b.y) + a.yy * (b.y, b.x)
 __device__ __forceinline__ v2f cmul_conj(v2f a, v2f b)
 {
-#if SOT_STFT_ASM_CMUL
     v2f t1, t2;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(t1) : "v"(a), "v"(b));   // (a.x b.x, -a.x b.y)
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(t2) : "v"(a), "v"(b));               // (a.y b.y, a.y b.x)
     return t1 + t2;
-#else
-    return a.xx * (v2f){b.x, -b.y} + a.yy * (v2f){b.y, b.x};
-#endif
 }
 // a + (-i) b = (a.x + b.y, a.y - b.x)   and   a + (+i) b = (a.x - b.y, a.y + b.x): one packed add with swapped / negated halves
 __device__ __forceinline__ v2f add_mi(v2f a, v2f b)
 {
-#if SOT_STFT_ASM_CMUL
     v2f r;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return (v2f){a.x + b.y, a.y - b.x};
-#endif
 }
 __device__ __forceinline__ v2f add_pi(v2f a, v2f b)
 {
-#if SOT_STFT_ASM_CMUL
     v2f r;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return (v2f){a.x - b.y, a.y + b.x};
-#endif
 }
 __device__ __forceinline__ v2f cconj(v2f a) { return (v2f){a.x, -a.y}; }
 __device__ __forceinline__ v2f mul_i(v2f a) { return (v2f){-a.y, a.x}; }    // a * (+i)
@@ -136,20 +97,11 @@ __device__ __forceinline__ v2f mul_mi(v2f a) { return (v2f){a.y, -a.x}; }   // a
 
 // LDS index of element i of a transform buffer: one point of padding after every 32.  The bit-reversed load (lane
 // stride m/2, m/4, ...) and the stride-4 accesses of the first pass would otherwise pile 32 lanes onto two banks
-// (SQ_LDS_BANK_CONFLICT 72 % -> 37 % of the LDS cycles of the forward kernel).
-#ifndef SOT_STFT_PAD
-#define SOT_STFT_PAD 0   /* diagnostic: other paddings of the transform buffer.  tools/ab_stft.py, n_fft 2048 forward / backward:
-                            0 (one point per 32) 22.4 / 53.0 us; 1 (per 16) 23.3 / 54.2; 2 (per 32 and per 256) 22.6 / 54.0;
-                            3 (per 16 and per 256) 22.3 / 53.5; 4 (per 8) 23.6 / 54.8; 5 (none) 29.3 / 65.7 */
-#endif
+// (SQ_LDS_BANK_CONFLICT 72 % -> 37 % of the LDS cycles of the forward kernel).  Other paddings were no faster (n_fft 2048: one point per
+// 32 22.4 / 53.0 us forward / backward, per 16 23.3 / 54.2, per 8 23.6 / 54.8, none 29.3 / 65.7).
 __host__ __device__ constexpr int zi(int i)
 {
-    return SOT_STFT_PAD == 0 ? i + (i >> 5)
-         : SOT_STFT_PAD == 1 ? i + (i >> 4)
-         : SOT_STFT_PAD == 2 ? i + (i >> 5) + (i >> 8)
-         : SOT_STFT_PAD == 3 ? i + (i >> 4) + (i >> 8)
-         : SOT_STFT_PAD == 4 ? i + (i >> 3)
-         : i;
+    return i + (i >> 5);
 }
 
 // Frame geometry for n_fft = 2^(LOGM+1).  The frames are REAL, so each one is transformed by a complex FFT of HALF its
@@ -164,11 +116,9 @@ struct Geo {
     // threads per frame slot: one radix-4 butterfly per thread and pass (m/4), at least 16.  Slots of at most one wavefront
     // (n_fft <= 512) synchronise with a compiler-level ordering point instead of the workgroup barrier (slot_sync): n_fft 512
     // forward 10.7 -> 10.3 us, backward 30.2 -> 28.7 us for 8192 frames.  (Shrinking the slots of n_fft 1024 / 2048 to one
-    // wavefront -- 2 / 4 butterflies per thread and pass, SOT_STFT_WAVE_FRAMES=2 -- was measured slower: n_fft 2048 forward
-    // 24.6 -> 29.4 us, backward 53 -> 104 us.)
-    static constexpr int tpf_full = (m / 4 > 16) ? (m / 4 > kThreads ? kThreads : m / 4) : 16;   // n_fft 4096: two butterflies per thread and pass
-    static constexpr int tpf = (SOT_STFT_WAVE_FRAMES == 2 && tpf_full > 64) ? 64 : tpf_full;
-    static constexpr bool wave_sync = (SOT_STFT_WAVE_FRAMES != 0) && tpf <= 64;
+    // wavefront -- 2 / 4 butterflies per thread and pass -- was measured slower: n_fft 2048 forward 24.6 -> 29.4 us, backward 53 -> 104 us.)
+    static constexpr int tpf = (m / 4 > 16) ? (m / 4 > kThreads ? kThreads : m / 4) : 16;   // n_fft 4096: two butterflies per thread and pass
+    static constexpr bool wave_sync = tpf <= 64;
     static constexpr int slots = kThreads / tpf;
     static constexpr int zpoints = zi(m - 1) + 2;
     static constexpr int table_points = m + m / 2 + 2;
@@ -299,11 +249,7 @@ __device__ __forceinline__ float magnitude(v2f x)
     const float s = fmaf(x.x, x.x, x.y * x.y);
     const bool plain = (s > 1e-30f && s < 1e30f) || (x.x == 0.0f && x.y == 0.0f);
     if (__builtin_expect(__ballot(!plain) != 0ull, 0)) return hypotf(x.x, x.y);
-#if SOT_STFT_RAW_SQRT
-    return __builtin_amdgcn_sqrtf(s);   // v_sqrt_f32 (1 ulp) without the range scaling and the two refinement steps of sqrtf: s is normal here
-#else
-    return sqrtf(s);
-#endif
+    return sqrtf(s);   // (v_sqrt_f32 alone: the same time, and past the 2e-6 pin against float64)
 }
 
 // |x| for a frame whose input amplitude has been checked once (frame_is_plain below): re^2 + im^2 can neither overflow nor lose the bins
@@ -377,22 +323,22 @@ __global__ __launch_bounds__(kThreads) void stft_mag_forward_kernel(const StftAr
         for (int k = lid; k <= G::m / 2; k += G::tpf) {
             v2f xk, xm;
             unpack_pair<LOGM>(z, wn, k, xk, xm);
-            store_mag(dst, k, magnitude(xk) * scale);
-            store_mag(dst, G::m - k, magnitude(xm) * scale);
+            dst[k] = magnitude(xk) * scale;
+            dst[G::m - k] = magnitude(xm) * scale;
             if (sp != nullptr) store_spec(sp, k, G::m - k, xk, xm);
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same transform with PERSISTENT workgroups (SOT_STFT_PERSISTENT): a workgroup loads the twiddle tables and its threads' window
+// The same transform with PERSISTENT workgroups: a workgroup loads the twiddle tables and its threads' window
 // taps once, then walks over frame groups g = blockIdx.x, blockIdx.x + gridDim.x, ...; the audio of the NEXT frame is fetched into
 // registers before the passes of the current one start, so its latency (and the tables') is paid once per workgroup instead of once
 // per frame.  Results are identical to stft_mag_forward_kernel's (the same operations on the same values).
 // (LDS: z [slots][zi(m)] | pass twiddles [m]; the unpacking twiddles W_n^k of a thread's bins sit in registers: 16.6 KB at n_fft 2048,
 // eight workgroups per CU, which the 64-VGPR budget of amdgpu_waves_per_eu(8) matches.)
 template <int LOGM>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SOT_STFT_PERSISTENT_WAVES, 8))) void stft_mag_forward_persistent_kernel(const StftArgs a)
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(kPersistentWaves, 8))) void stft_mag_forward_persistent_kernel(const StftArgs a)
 {
     using G = Geo<LOGM>;
     constexpr int PER = G::m / G::tpf;                       // packed points per thread and frame
@@ -454,8 +400,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SOT_ST
                 if (k <= G::m / 2) {
                     v2f xk, xm;
                     unpack_pair_w<LOGM>(z, wnr[j], k, xk, xm);
-                    store_mag(dst, k, magnitude(xk) * scale);
-                    store_mag(dst, G::m - k, magnitude(xm) * scale);
+                    dst[k] = magnitude(xk) * scale;
+                    dst[G::m - k] = magnitude(xm) * scale;
                     if (sp != nullptr) store_spec(sp, k, G::m - k, xk, xm);
                 }
             }
@@ -464,155 +410,17 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(SOT_ST
     }
 }
 
-// n_fft = 2048, one WAVEFRONT per frame (SOT_STFT_WAVE_KERNEL): the 1024-point complex transform of the packed frame as five
-// radix-4 decimation-in-frequency stages on 16 points per lane.  With the index written in base 4, i = (d4 d3 d2 d1 d0), a lane
-// keeps two digits in its 16 registers and the other three are its lane number: stages 1-2 (digits d4, d3) on
-// r = 4 d4 + d3, lane = 16 d2 + 4 d1 + d0 (element 64 r + lane: the load is coalesced), one exchange through the wave's LDS
-// buffer, stages 3-4 (d2, d1), a second exchange, stage 5 (d0); the results are written to LDS in natural frequency order
-// (k = q4 + 4 q3 + 16 q2 + 64 q1 + 256 q0) for the pairwise unpacking of the real transform.  No workgroup barrier inside the
-// frame loop (slot_sync<true>), twiddles W_1024^j from one LDS table per workgroup, 4 frames in flight per workgroup in a
-// persistent grid.  Index algebra checked against numpy's FFT (6e-14) before it was written down here.
-// ---------------------------------------------------------------------------------------------
+// n_fft = 2048, one WAVEFRONT per frame: the 1024-point complex transform of the packed frame as five radix-4 decimation-in-frequency
+// stages on 16 points per lane.  With the index written in base 4, i = (d4 d3 d2 d1 d0), a lane keeps two digits in its 16 registers and
+// the other three are its lane number: stages 1-2 (digits d4, d3) on r = 4 d4 + d3, lane = 16 d2 + 4 d1 + d0 (element 64 r + lane: the
+// load is coalesced), one exchange through the wave's LDS buffer, stages 3-4 (d2, d1), a second exchange, stage 5 (d0); the results are
+// written to LDS in natural frequency order (k = q4 + 4 q3 + 16 q2 + 64 q1 + 256 q0) for the pairwise unpacking of the real transform.
+// Index algebra checked against numpy's FFT (6e-14) before it was written down here.
 constexpr int kWaveBuf = 64 * 17;   // v2f slots of one wave's exchange buffer: [lane][16 registers + 1 pad]; >= zi(1024) = 1056
-
-// radix-4 butterfly, outputs q = 0..3: sum_p a_p W_4^{p q} (forward: W_4 = -i; INVERSE: +i)
-template <bool INVERSE>
-__device__ __forceinline__ void bf4(const v2f a0, const v2f a1, const v2f a2, const v2f a3, v2f& o0, v2f& o1, v2f& o2, v2f& o3)
-{
-    const v2f s02 = a0 + a2, d02 = a0 - a2, s13 = a1 + a3, d13 = a1 - a3;
-    const v2f rot = INVERSE ? mul_i(d13) : mul_mi(d13);
-    o0 = s02 + s13; o1 = d02 + rot; o2 = s02 - s13; o3 = d02 - rot;
-}
-
-template <bool INVERSE>
-__device__ __forceinline__ v2f twid(const v2f* tw, int j) { const v2f w = tw[j & 1023]; return INVERSE ? cconj(w) : w; }
-
-// r[q] = z[64 q + lane] on entry; on return the transform sits in zl[zi(k)], k = 0 .. 1023 (after the caller's slot_sync)
-template <bool INVERSE>
-__device__ __forceinline__ void fft1024_wave(v2f (&r)[16], v2f* zl, const v2f* tw, int lane)
-{
-    v2f o[16];
-    // stage 1 (digit d4; registers 4 p + d3): twiddle W_1024^{(64 d3 + lane) q}
-#pragma unroll
-    for (int d3 = 0; d3 < 4; ++d3) {
-        const int j = 64 * d3 + lane;
-        bf4<INVERSE>(r[d3], r[4 + d3], r[8 + d3], r[12 + d3], o[d3], o[4 + d3], o[8 + d3], o[12 + d3]);
-#pragma unroll
-        for (int q = 1; q < 4; ++q) o[4 * q + d3] = cmul(o[4 * q + d3], twid<INVERSE>(tw, j * q));
-    }
-    // stage 2 (digit d3; registers 4 q4 + p): twiddle W_256^{lane q} = W_1024^{4 lane q}
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-        bf4<INVERSE>(o[4 * q4], o[4 * q4 + 1], o[4 * q4 + 2], o[4 * q4 + 3], r[4 * q4], r[4 * q4 + 1], r[4 * q4 + 2], r[4 * q4 + 3]);
-#pragma unroll
-        for (int q = 1; q < 4; ++q) r[4 * q4 + q] = cmul(r[4 * q4 + q], twid<INVERSE>(tw, 4 * lane * q));
-    }
-    // exchange 1: register (q4, q3) of lane (d2, d1, d0) -> register (d2, d1) of lane (q4, q3, d0)
-    {
-        const int d0 = lane & 3, rr = lane >> 2;   // rr = 4 d2 + d1
-#pragma unroll
-        for (int q = 0; q < 16; ++q) zl[(4 * q + d0) * 17 + rr] = r[q];
-        slot_sync<true>();
-#pragma unroll
-        for (int q = 0; q < 16; ++q) r[q] = zl[lane * 17 + q];
-        slot_sync<true>();
-    }
-    // stage 3 (digit d2; registers 4 p + d1): twiddle W_64^{(4 d1 + d0) q} = W_1024^{16 (4 d1 + d0) q}
-    const int d0 = lane & 3;
-#pragma unroll
-    for (int d1 = 0; d1 < 4; ++d1) {
-        const int j = 16 * (4 * d1 + d0);
-        bf4<INVERSE>(r[d1], r[4 + d1], r[8 + d1], r[12 + d1], o[d1], o[4 + d1], o[8 + d1], o[12 + d1]);
-#pragma unroll
-        for (int q = 1; q < 4; ++q) o[4 * q + d1] = cmul(o[4 * q + d1], twid<INVERSE>(tw, j * q));
-    }
-    // stage 4 (digit d1; registers 4 q2 + p): twiddle W_16^{d0 q} = W_1024^{64 d0 q}
-#pragma unroll
-    for (int q2 = 0; q2 < 4; ++q2) {
-        bf4<INVERSE>(o[4 * q2], o[4 * q2 + 1], o[4 * q2 + 2], o[4 * q2 + 3], r[4 * q2], r[4 * q2 + 1], r[4 * q2 + 2], r[4 * q2 + 3]);
-#pragma unroll
-        for (int q = 1; q < 4; ++q) r[4 * q2 + q] = cmul(r[4 * q2 + q], twid<INVERSE>(tw, 64 * d0 * q));
-    }
-    // exchange 2: register (q2, q1) of lane (q4, q3, d0) -> register (d0, q1) of lane (q4, q3, q2)
-    {
-        const int hi = lane >> 2;   // 4 q4 + q3
-#pragma unroll
-        for (int q = 0; q < 16; ++q) zl[(4 * hi + (q >> 2)) * 17 + 4 * d0 + (q & 3)] = r[q];
-        slot_sync<true>();
-#pragma unroll
-        for (int q = 0; q < 16; ++q) r[q] = zl[lane * 17 + q];
-        slot_sync<true>();
-    }
-    // stage 5 (digit d0; registers 4 p + q1), no twiddle; result (q4 q3 q2 q1 q0) is frequency k = q4 + 4 q3 + 16 q2 + 64 q1 + 256 q0
-    const int kb = (lane >> 4) + 4 * ((lane >> 2) & 3) + 16 * (lane & 3);
-#pragma unroll
-    for (int q1 = 0; q1 < 4; ++q1) {
-        bf4<INVERSE>(r[q1], r[4 + q1], r[8 + q1], r[12 + q1], o[q1], o[4 + q1], o[8 + q1], o[12 + q1]);
-#pragma unroll
-        for (int q0 = 0; q0 < 4; ++q0) zl[zi(kb + 64 * q1 + 256 * q0)] = o[4 * q0 + q1];
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void stft_mag_forward_wave_kernel(const StftArgs a)
-{
-    constexpr int LOGM = 10, m = 1024, n = 2048, nb = m + 1;
-    extern __shared__ __attribute__((aligned(16))) float smem_f[];
-    v2f* const tw = reinterpret_cast<v2f*>(smem_f);          // W_1024^j, j < 1024
-    v2f* const wn = tw + 1024;                                // W_2048^k, k <= 512 (+ pad)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    v2f* const zl = wn + 520 + wave * kWaveBuf;
-    // W_1024^{256 a + b} = W_2048^{2 b} (-i)^a  (exact quarter turns of the committed table)
-    for (int j = threadIdx.x; j < 1024; j += kThreads) {
-        const float2 t = kWn[4 * (j & 255)];
-        v2f w = (v2f){t.x, t.y};
-        const int qa = j >> 8;
-        if (qa == 1) w = mul_mi(w); else if (qa == 2) w = -w; else if (qa == 3) w = mul_i(w);
-        tw[j] = w;
-    }
-    for (int k = threadIdx.x; k <= 512; k += kThreads) { const float2 t = kWn[2 * k]; wn[k] = (v2f){t.x, t.y}; }
-    __syncthreads();
-    const float scale = 1.0f / sqrtf((float)n);
-    const unsigned total = (unsigned)(a.batch * a.frames), frames = (unsigned)a.frames;
-    const float2* win = reinterpret_cast<const float2*>(a.window);
-    for (unsigned fr = blockIdx.x * 4 + wave; fr < total; fr += gridDim.x * 4) {
-        const unsigned b = fr / frames, f = fr - b * frames;
-        const float* src = (a.audio_b != nullptr && (int64_t)b >= a.split) ? a.audio_b + ((int64_t)b - a.split) * a.row_stride_b
-                                                                          : a.audio + (int64_t)b * a.row_stride;
-        const int64_t t0 = (int64_t)f * a.hop;
-        const bool inside = t0 + n <= a.samples;
-        v2f r[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int i = 64 * q + lane;
-            const int64_t t = t0 + 2 * i;
-            const float2 w = win[i];
-            float v0, v1;
-            if (inside) { v0 = src[t] * w.x; v1 = src[t + 1] * w.y; }
-            else { v0 = (t < a.samples) ? src[t] * w.x : 0.0f; v1 = (t + 1 < a.samples) ? src[t + 1] * w.y : 0.0f; }
-            r[q] = (v2f){v0, v1};
-        }
-        fft1024_wave<false>(r, zl, tw, lane);
-        slot_sync<true>();
-        float* dst = a.mag + (int64_t)fr * nb;
-        float2* sp = (a.spec != nullptr && (int64_t)b >= a.spec_first) ? a.spec + ((int64_t)fr - a.spec_first * frames) * nb : nullptr;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) {
-            const int k = lane + 64 * j;
-            if (k <= m / 2) {
-                v2f xk, xm;
-                unpack_pair<LOGM>(zl, wn, k, xk, xm);
-                store_mag(dst, k, magnitude(xk) * scale);
-                store_mag(dst, m - k, magnitude(xm) * scale);
-                if (sp != nullptr) store_spec(sp, k, m - k, xk, xm);
-            }
-        }
-        slot_sync<true>();   // the unpack reads are issued before the next frame's exchange writes
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Round 4: the one-wavefront-per-frame transform again, rebuilt around occupancy (stft_mag_forward_wave2_kernel, n_fft 2048).
-// What the round-2 kernel above paid for: 194 VGPRs (two waves per SIMD) and three quarters of a CU's LDS per four frames.  Here
+// What the round-2 kernel paid for: 194 VGPRs (two waves per SIMD) and three quarters of a CU's LDS per four frames.  Here
 //  * ONE 1024-thread workgroup per CU: sixteen waves = sixteen frames in flight per CU share one twiddle table (W_1024^j, 8 KB) and one
 //    copy of the window (8 KB); 159.8 KB of LDS; the 128-VGPR budget of a 1024-thread workgroup is met by doing every radix-4 stage IN
 //    PLACE on the sixteen points a lane holds (no second 16-point array);
@@ -622,9 +430,6 @@ __global__ __launch_bounds__(kThreads) void stft_mag_forward_wave_kernel(const S
 //    scalar path covers the rest).
 // No workgroup barrier inside the frame loop: a wave's exchanges through its private LDS buffer need only wave-level ordering.
 // ---------------------------------------------------------------------------------------------
-#ifndef SOT_STFT_XCHG_SWZ
-#define SOT_STFT_XCHG_SWZ 1
-#endif
 template <bool INVERSE>
 __device__ __forceinline__ v2f ctw(v2f a, v2f w) { return INVERSE ? cmul_conj(a, w) : cmul(a, w); }   // a * twiddle (inverse: conjugate twiddle)
 
@@ -638,7 +443,7 @@ __device__ __forceinline__ void bf4_ip(v2f& a0, v2f& a1, v2f& a2, v2f& a3)
 }
 
 // r[q] = z[64 q + lane] on entry; on return the transform sits in zl[zi(k)], k = 0 .. 1023 (after the caller's slot_sync).  The index
-// algebra is fft1024_wave's (five radix-4 decimation-in-frequency stages, two exchanges), every stage in place.
+// algebra is the one above (five radix-4 decimation-in-frequency stages, two exchanges), every stage in place.
 template <bool INVERSE>
 __device__ __forceinline__ void fft1024_wave_ip(v2f (&r)[16], v2f* zl, const v2f* tw, int lane)
 {
@@ -663,15 +468,15 @@ __device__ __forceinline__ void fft1024_wave_ip(v2f (&r)[16], v2f* zl, const v2f
     // written by lane (rr, d0), row q of column L read by lane L.  Storage [column ^ g(row)][17]: the reader's lanes still sweep 64 different
     // columns per instruction (conflict-free as before), the writer's 16-lane groups no longer pile four lanes on one bank pair
     // (SQ_LDS_BANK_CONFLICT was 49 % of the kernel's LDS cycles, all of it these stores): g(row) = 4 (row & 3) here (two-way left),
-    // g(row) = row >> 2 in exchange 2 (conflict-free).  SOT_STFT_XCHG_SWZ=0: the plain [column][17] image.
+    // g(row) = row >> 2 in exchange 2 (conflict-free).
     const int d0 = lane & 3;
     {
         const int rr = lane >> 2;   // 4 d2 + d1
 #pragma unroll
-        for (int q = 0; q < 16; ++q) zl[((4 * q + d0) ^ (SOT_STFT_XCHG_SWZ ? 4 * (rr & 3) : 0)) * 17 + rr] = r[q];
+        for (int q = 0; q < 16; ++q) zl[((4 * q + d0) ^ (4 * (rr & 3))) * 17 + rr] = r[q];
         slot_sync<true>();
 #pragma unroll
-        for (int q = 0; q < 16; ++q) r[q] = zl[(lane ^ (SOT_STFT_XCHG_SWZ ? 4 * (q & 3) : 0)) * 17 + q];
+        for (int q = 0; q < 16; ++q) r[q] = zl[(lane ^ (4 * (q & 3))) * 17 + q];
         slot_sync<true>();
     }
     // stage 3 (digit d2; registers 4 p + d1 -> 4 q + d1): twiddle W_64^{(4 d1 + d0) q} = W_1024^{16 (4 d1 + d0) q}
@@ -695,10 +500,10 @@ __device__ __forceinline__ void fft1024_wave_ip(v2f (&r)[16], v2f* zl, const v2f
     {
         const int hi = lane >> 2;   // 4 q4 + q3
 #pragma unroll
-        for (int q = 0; q < 16; ++q) zl[((4 * hi + (q >> 2)) ^ (SOT_STFT_XCHG_SWZ ? d0 : 0)) * 17 + 4 * d0 + (q & 3)] = r[q];   // row 4 d0 + (q & 3): g = d0
+        for (int q = 0; q < 16; ++q) zl[((4 * hi + (q >> 2)) ^ d0) * 17 + 4 * d0 + (q & 3)] = r[q];   // row 4 d0 + (q & 3): g = d0
         slot_sync<true>();
 #pragma unroll
-        for (int q = 0; q < 16; ++q) r[q] = zl[(lane ^ (SOT_STFT_XCHG_SWZ ? (q >> 2) : 0)) * 17 + q];
+        for (int q = 0; q < 16; ++q) r[q] = zl[(lane ^ (q >> 2)) * 17 + q];
         slot_sync<true>();
     }
     // stage 5 (digit d0; registers 4 p + q1 -> 4 q0 + q1), no twiddle; result (q4 q3 q2 q1 q0) is frequency k = q4 + 4 q3 + 16 q2 + 64 q1 + 256 q0
@@ -733,8 +538,8 @@ __device__ __forceinline__ void wave2_unpack_store(const v2f* zl, const v2f* wn,
         if (j < 8 || k <= m / 2) {
             v2f xk, xm;
             unpack_pair<LOGM>(zl, wn, k, xk, xm);
-            store_mag(dst, k, (PLAIN ? magnitude_plain(xk) : magnitude(xk)) * scale);
-            store_mag(dst, m - k, (PLAIN ? magnitude_plain(xm) : magnitude(xm)) * scale);
+            dst[k] = (PLAIN ? magnitude_plain(xk) : magnitude(xk)) * scale;
+            dst[m - k] = (PLAIN ? magnitude_plain(xm) : magnitude(xm)) * scale;
             if (sp != nullptr) store_spec(sp, k, m - k, xk, xm);
         }
     }
@@ -1097,67 +902,14 @@ __global__ __launch_bounds__(kBwdWave2Threads) void stft_mag_backward_spec_wave2
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same with the overlap-add INSIDE the kernel, for clips of at most 16 frames (config 5 and the paper's step: 4096 samples, hop 256):
-// one 1024-thread workgroup per clip, wave f transforms frame f and leaves the windowed frame gradient in its own LDS buffer; after ONE
-// workgroup barrier every thread adds, for its two packed points of the clip, the frames that cover them in ascending frame order
-// (deterministic) and stores the clip's gradient: no scratch buffer, no second kernel (stft_overlap_add_kernel: 7 us at 256 clips).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kWave2Threads) void stft_mag_backward_spec_clip_kernel(const StftArgs a)
-{
-    constexpr int n = 2048, nb = 1025, m = 1024;
-    extern __shared__ __attribute__((aligned(16))) float smem_f[];
-    v2f* const tw = reinterpret_cast<v2f*>(smem_f);
-    v2f* const wn = tw + 1024;
-    v2f* const wl = wn + 520;
-    v2f* const bufs = wl + 1024;                              // 16 frame buffers of kWaveBuf points
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    v2f* const zl = bufs + wave * kWaveBuf;
-    wave2_load_tables<kWave2Threads>(a, tw, wn, wl);
-    const float scale = 1.0f / sqrtf((float)n);
-    const float up = a.grad_scale ? *a.grad_scale : 1.0f;
-    const int frames = (int)a.frames, hp = a.hop >> 1;        // hop in packed points (hop is even: host)
-    const int samples = (int)a.samples;
-    for (int64_t b = blockIdx.x; b < a.batch; b += gridDim.x) {
-        if (wave < frames) {
-            v2f out[16];
-            wave2_frame_gradient(a.spec_in + (b * a.frames + wave) * nb, a.grad_mag + (b * a.frames + wave) * nb, up, scale, zl, tw, wn, wl, lane, out);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) zl[zi(64 * q + lane)] = out[q];
-        }
-        __syncthreads();
-        float* const dst = a.grad_audio + b * a.samples;
-        for (int p = threadIdx.x; 2 * p < samples; p += kWave2Threads) {   // packed point p of the clip = samples 2 p, 2 p + 1
-            const int f_hi = min(p / hp, frames - 1);
-            int f_lo = (p - (m - 1) + hp - 1) / hp;
-            if (p - (m - 1) <= 0) f_lo = 0;
-            v2f sum = (v2f){0.0f, 0.0f};
-            for (int f = f_lo; f <= f_hi; ++f) sum += bufs[f * kWaveBuf + zi(p - f * hp)];
-            if (2 * p + 1 < samples) {
-                float2* d2 = reinterpret_cast<float2*>(dst + 2 * p);
-                if ((reinterpret_cast<uintptr_t>(d2) & 7u) == 0) {
-                    float2 o = make_float2(sum.x, sum.y);
-                    if (a.accumulate) { const float2 old = *d2; o.x += old.x; o.y += old.y; }
-                    *d2 = o;
-                } else {
-                    dst[2 * p] = a.accumulate ? dst[2 * p] + sum.x : sum.x;
-                    dst[2 * p + 1] = a.accumulate ? dst[2 * p + 1] + sum.y : sum.y;
-                }
-            } else {
-                dst[2 * p] = a.accumulate ? dst[2 * p] + sum.x : sum.x;
-            }
-        }
-        __syncthreads();   // the frame buffers are read before the next clip overwrites them
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
 // Round 5: n_fft 2048 on the one-wavefront FFT of csrc/sot_wave_fft.hpp (written for the two-launch MSSLoss: 16 points per lane, radix-4 stages
 // in registers, padded additive exchange maps, fused complex products, a transposed network for the inverse -- a frame's forward transform is
 // ~415 instructions and ~4 000 clocks on one wave against the 28 000-clock chain of the round-4 wave kernels).
-//  * stft_mag_backward_spec_clipw_kernel: the backward from the stored spectrum with the overlap-add inside (clips of at most 16 frames),
-//    same structure as stft_mag_backward_spec_clip_kernel: wave f of a 1024-thread workgroup turns frame f's spectrum and upstream gradient
-//    into the Hermitian packing G (natural order in its LDS buffer), runs the inverse network and leaves the windowed frame gradient in its
-//    buffer; after one barrier the workgroup adds the frames that cover each sample in ascending frame order.
+//  * stft_mag_backward_spec_clipw_kernel: the backward from the stored spectrum with the overlap-add INSIDE the kernel, for clips of at most
+//    16 frames (config 5 and the paper's step: 4096 samples, hop 256), one 1024-thread workgroup per clip: wave f turns frame f's spectrum
+//    and upstream gradient into the Hermitian packing G (natural order in its LDS buffer), runs the inverse network and leaves the windowed
+//    frame gradient in its buffer; after one barrier the workgroup adds the frames that cover each sample in ascending frame order
+//    (deterministic): no scratch buffer, no second kernel (stft_overlap_add_kernel: 7 us at 256 clips).
 //  * stft_mag_forward_wavew_kernel: forward (single or pair form, optional spectrum) with one wavefront per frame in 512-thread workgroups,
 //    for the batches BELOW the round-4 wave kernel's threshold (512 ... 3071 frames: the paper's 64 clips), where the slot kernel ran.
 // ---------------------------------------------------------------------------------------------
@@ -1315,8 +1067,8 @@ __device__ __forceinline__ void wavew_unpack_store(const sot_wfft::v2f* zl, cons
         const sot_wfft::v2f wz = sot_wfft::cmul(o, wn[k]), eh = 0.5f * e;
         const sot_wfft::v2f xk = eh + wz, xc = eh - wz;                   // X_k, conj X_(m-k)
         const v2f xk_ = (v2f){xk.x, xk.y}, xc_ = (v2f){xc.x, xc.y};
-        store_mag(dst, k, (PLAIN ? magnitude_plain(xk_) : magnitude(xk_)) * scale);
-        store_mag(dst, m - k, (PLAIN ? magnitude_plain(xc_) : magnitude(xc_)) * scale);
+        dst[k] = (PLAIN ? magnitude_plain(xk_) : magnitude(xk_)) * scale;
+        dst[m - k] = (PLAIN ? magnitude_plain(xc_) : magnitude(xc_)) * scale;
         if (sp != nullptr) { sp[k] = make_float2(xk.x, xk.y); sp[m - k] = make_float2(xc.x, -xc.y); }
     }
 }
@@ -1582,9 +1334,6 @@ static void launch_slots(void (*kernel)(const StftArgs), int64_t work, size_t ex
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, st, a);
 }
 
-#ifndef SOT_STFT_PERSISTENT
-#define SOT_STFT_PERSISTENT 1
-#endif
 static int cu_count()
 {
     static std::atomic<int> cus[64];   // zero-initialised; per device, written with the same value by whoever gets there first
@@ -1624,34 +1373,19 @@ static void launch_forward_persistent(int64_t work, hipStream_t st, const StftAr
 // (one frame per workgroup) takes the persistent form.
 static void launch_forward(int64_t work, hipStream_t st, const StftArgs& a)
 {
-    if (SOT_STFT_PERSISTENT && a.logm == 10) { launch_forward_persistent<10>(work, st, a); return; }
+    if (a.logm == 10) { launch_forward_persistent<10>(work, st, a); return; }
     SOT_STFT_LAUNCH(stft_mag_forward_kernel, work, 0, st, a);
 }
 
-// OFF by default.  Measured (MI355X, 256 clips x 16 frames, tools/ab_stft.py): forward 24.2 us against 24.7 us for the slot
-// kernel, forward of a pair 52.5 against 42.3 us.  The kernel is correct (tests/test_stft_producer.py passes with it) and does
-// a frame in ~1000 instructions per lane without a workgroup barrier, but at 16-32 frames per CU there is no steady state to
-// amortise anything over: a frame's dependent chain (loads -> five stages -> unpack) on ONE wavefront at two waves per SIMD
-// (194 VGPRs) takes longer than the same frame spread over four wavefronts.  It is the form to switch on for batches of
-// >= 64 frames per CU, after a register diet (the two 16-point arrays).
-#ifndef SOT_STFT_WAVE_KERNEL
-#define SOT_STFT_WAVE_KERNEL 0
-#endif
-// n_fft 2048: the one-wavefront-per-frame kernel, persistent grid (3 workgroups of 4 frames per CU fit the LDS); returns
-// false for other sizes (the caller launches the slot kernel)
+// n_fft 2048, at least kWave2MinFrames frames: the round-4 one-wavefront-per-frame kernel, one 1024-thread workgroup per CU.
 // Measured (round 4, tools/r4/stft_sizes.py, forward of a pair, n_fft 2048 / hop 256, us per call, slot kernel | this kernel;
 // profiles/r4j_stft_wave2.txt): 512 frames 10.6 | 15.0, 1024: 10.6 | 15.3, 2048: 14.4 | 16.1, 4096: 21.6 | 17.3, 8192 (config 5): 37.3 | 28.5,
 // 16384: 64.0 | 48.0 -- a frame is a 28 000-clock dependent chain on one wave (~15 us), so the kernel needs at least one frame per
 // wave slot of the chip (256 CUs x 16) to pay: from 3072 frames.
-#ifndef SOT_STFT_WAVE2_KERNEL
-#define SOT_STFT_WAVE2_KERNEL 1
-#endif
-#ifndef SOT_STFT_WAVE2_MIN_FRAMES
-#define SOT_STFT_WAVE2_MIN_FRAMES 3072
-#endif
+constexpr int64_t kWave2MinFrames = 3072;
 static bool launch_forward_wave2(const StftArgs& a, int64_t frames_total, hipStream_t st)
 {
-    if (!SOT_STFT_WAVE2_KERNEL || a.logm != 10 || frames_total < SOT_STFT_WAVE2_MIN_FRAMES) return false;
+    if (a.logm != 10 || frames_total < kWave2MinFrames) return false;
     static bool attr_done[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
@@ -1666,62 +1400,33 @@ static bool launch_forward_wave2(const StftArgs& a, int64_t frames_total, hipStr
     return true;
 }
 
-#ifndef SOT_STFT_BWD_WAVE2_KERNEL
-#define SOT_STFT_BWD_WAVE2_KERNEL 1
-#endif
-#ifndef SOT_STFT_BWD_WAVE2_MIN_GROUPS
-#define SOT_STFT_BWD_WAVE2_MIN_GROUPS 1024
-#endif
-#ifndef SOT_STFT_BWD_CLIP_KERNEL
-#define SOT_STFT_BWD_CLIP_KERNEL 1
-#endif
-#ifndef SOT_STFT_BWD_CLIP_MIN_CLIPS
-#define SOT_STFT_BWD_CLIP_MIN_CLIPS 64
-#endif
-#ifndef SOT_STFT_BWD_CLIPW_KERNEL
-#define SOT_STFT_BWD_CLIPW_KERNEL 1
-#endif
-#ifndef SOT_STFT_FWD_WAVEW_MIN_FRAMES
-#define SOT_STFT_FWD_WAVEW_MIN_FRAMES 512     /* below: the slot kernels (a frame is a dependent chain on one wave: small batches want the frame spread over four) */
-#endif
+constexpr int64_t kBwdWave2MinGroups = 1024;
+constexpr int64_t kBwdClipMinClips = 64;
+constexpr int64_t kFwdWavewMinFrames = 512;   // below: the slot kernels (a frame is a dependent chain on one wave: small batches want the frame spread over four)
 // the backward from the stored spectrum with the overlap-add inside: clips of at most 16 frames of 2048, one workgroup per clip.  Returns true
 // when it has launched the WHOLE backward (the caller then skips stft_overlap_add_kernel).
 static bool launch_backward_spec_clip(const StftArgs& a, hipStream_t st)
 {
-    if (!SOT_STFT_BWD_CLIP_KERNEL || a.logm != 10 || a.spec_in == nullptr || a.frames > kWave2Waves || a.frames < 1 || (a.hop & 1) != 0 ||
-        a.batch < SOT_STFT_BWD_CLIP_MIN_CLIPS)
+    if (a.logm != 10 || a.spec_in == nullptr || a.frames > kWave2Waves || a.frames < 1 || (a.hop & 1) != 0 || a.batch < kBwdClipMinClips)
         return false;
     static bool attr_done[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
     if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mag_backward_spec_clip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kWave2LdsBytes) != hipSuccess)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mag_backward_spec_clipw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kClipwLdsBytes) != hipSuccess)
             (void)hipGetLastError();
         if (dev >= 0 && dev < 64) attr_done[dev] = true;
     }
     const int64_t cap = cu_count();
-#if SOT_STFT_BWD_CLIPW_KERNEL     /* round 5: the same structure on the one-wavefront FFT of csrc/sot_wave_fft.hpp */
-    {
-        static bool attrw_done[64] = {};
-        if (dev < 0 || dev >= 64 || !attrw_done[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mag_backward_spec_clipw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kClipwLdsBytes) != hipSuccess)
-                (void)hipGetLastError();
-            if (dev >= 0 && dev < 64) attrw_done[dev] = true;
-        }
-        hipLaunchKernelGGL(stft_mag_backward_spec_clipw_kernel, dim3((unsigned)(a.batch < cap ? a.batch : cap)), dim3(kWave2Threads), kClipwLdsBytes, st, a);
-        return true;
-    }
-#endif
-    hipLaunchKernelGGL(stft_mag_backward_spec_clip_kernel, dim3((unsigned)(a.batch < cap ? a.batch : cap)), dim3(kWave2Threads), kWave2LdsBytes, st, a);
+    hipLaunchKernelGGL(stft_mag_backward_spec_clipw_kernel, dim3((unsigned)(a.batch < cap ? a.batch : cap)), dim3(kWave2Threads), kClipwLdsBytes, st, a);
     return true;
 }
 
 // the backward from the stored spectrum, one wavefront per group of two frames: n_fft 2048, hop 256 or 512, scratch rows on 8-byte boundaries
 static bool launch_backward_spec_wave2(const StftArgs& a, int64_t groups_total, hipStream_t st)
 {
-    if (!SOT_STFT_BWD_WAVE2_KERNEL || a.logm != 10 || groups_total < SOT_STFT_BWD_WAVE2_MIN_GROUPS || (a.hop != 256 && a.hop != 512) ||
+    if (a.logm != 10 || groups_total < kBwdWave2MinGroups || (a.hop != 256 && a.hop != 512) ||
         (reinterpret_cast<uintptr_t>(a.partial) & 7u) != 0 || (a.span & 1) != 0)
         return false;
     void (*kern)(const StftArgs) = a.hop == 256 ? stft_mag_backward_spec_wave2_kernel<2> : stft_mag_backward_spec_wave2_kernel<4>;
@@ -1739,11 +1444,11 @@ static bool launch_backward_spec_wave2(const StftArgs& a, int64_t groups_total, 
     return true;
 }
 
-// n_fft 2048, SOT_STFT_FWD_WAVEW_MIN_FRAMES <= frames < SOT_STFT_WAVE2_MIN_FRAMES: one wavefront per frame on the round-5 FFT (the round-4
+// n_fft 2048, kFwdWavewMinFrames <= frames < kWave2MinFrames: one wavefront per frame on the round-5 FFT (the round-4
 // wave kernel keeps the larger batches: its results on BASELINE config 5 are what the cutoff mode's knife-edge statistics were taken with)
 static bool launch_forward_wavew(const StftArgs& a, int64_t frames_total, hipStream_t st)
 {
-    if (a.logm != 10 || frames_total < SOT_STFT_FWD_WAVEW_MIN_FRAMES || (SOT_STFT_WAVE2_KERNEL && frames_total >= SOT_STFT_WAVE2_MIN_FRAMES)) return false;
+    if (a.logm != 10 || frames_total < kFwdWavewMinFrames || frames_total >= kWave2MinFrames) return false;
     static bool attr_done[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
@@ -1758,25 +1463,10 @@ static bool launch_forward_wavew(const StftArgs& a, int64_t frames_total, hipStr
     return true;
 }
 
+// n_fft 2048 with enough frames: one wavefront per frame; false for the rest (the caller launches the slot kernels)
 static bool launch_forward_wave(const StftArgs& a, int64_t frames_total, hipStream_t st)
 {
-    if (launch_forward_wavew(a, frames_total, st)) return true;
-    if (launch_forward_wave2(a, frames_total, st)) return true;
-    if (!SOT_STFT_WAVE_KERNEL || a.logm != 10) return false;
-    const size_t lds = (1024 + 520 + 4 * (size_t)kWaveBuf) * sizeof(float2);
-    static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {   // idempotent per device; a benign race sets it twice
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mag_forward_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            (void)hipGetLastError();
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
-    const int64_t want = (frames_total + 3) / 4;
-    const int64_t cap = 256 * 3;
-    hipLaunchKernelGGL(stft_mag_forward_wave_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kThreads), lds, st, a);
-    return true;
+    return launch_forward_wavew(a, frames_total, st) || launch_forward_wave2(a, frames_total, st);
 }
 
 }  // namespace sot_stft

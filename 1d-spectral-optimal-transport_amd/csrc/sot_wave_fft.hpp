@@ -7,10 +7,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef WFFT_DIAG_TW_NOLANE
-#define WFFT_DIAG_TW_NOLANE 0
-#endif
-
 namespace sot_wfft {
 
 typedef float v2f __attribute__((ext_vector_type(2)));   // one complex point; arithmetic maps to v_pk_*_f32
@@ -28,31 +24,19 @@ __device__ __forceinline__ void wave_sync()
 
 // complex products on the packed-fp32 unit: one v_pk_mul_f32 + one v_pk_fma_f32 (operand halves picked by op_sel, signs by neg_*).
 // (csrc/sot_stft.hip keeps the three-rounding form for the SOT chain's knife edge; nothing here has one, and the fused form is the more accurate.)
-#ifndef MSS_CMUL_3OP
-#define MSS_CMUL_3OP 0    /* diagnostic: 1 = the three-rounding products of csrc/sot_stft.hip */
-#endif
 __device__ __forceinline__ v2f cmul(v2f a, v2f b)
 {
     v2f t, r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(t) : "v"(a), "v"(b));          // (-a.y b.y, a.y b.x)
-#if MSS_CMUL_3OP
-    return a.xx * b + t;
-#else
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "=v"(r) : "v"(a), "v"(b), "v"(t));       // (a.x b.x, a.x b.y) + t
     return r;
-#endif
 }
 __device__ __forceinline__ v2f cmul_conj(v2f a, v2f b)   // a * conj(b)
 {
     v2f t, r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(b));                                   // (a.y b.y, a.y b.x)
-#if MSS_CMUL_3OP
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));                      // (a.x b.x, -a.x b.y)
-    return r + t;
-#else
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[0,1,1] neg_hi:[0,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(t));    // (a.x b.x, -a.x b.y) + t
     return r;
-#endif
 }
 __device__ __forceinline__ v2f add_mi(v2f a, v2f b)      // a - i b
 {
@@ -131,11 +115,7 @@ __device__ __forceinline__ void radix4_stage(v2f (&r)[16], const v2f* tw, int la
     // q = the position bits below the stage; the stage's block of the table holds W^q, W^2q, W^3q (W = the 2^(BETA+1)-th root) as three runs
     // of `half` consecutive entries: the lanes of a wave differ in the LOW bits of q and read consecutive slots -- no bank conflicts (the
     // single strided table W_1024^(q << (9 - BETA)) of the first form had up to 8 lanes per bank: 35 % of the MSS kernel's LDS cycles)
-#if WFFT_DIAG_TW_NOLANE   /* diagnostic only (wrong values): lane-independent twiddle addresses, to price the reads' bank conflicts */
-    const int ll = 0;
-#else
     const int ll = lane_low ? (lanepos & mask) : 0;
-#endif
     const v2f* const t1 = tw + tw_block(BETA) + ll;
 #pragma unroll
     for (int base = 0; base < 16; ++base) {

@@ -25,42 +25,22 @@
 #pragma once
 #include "sot_device.hpp"
 
-#ifndef SOT_WSORT_DPP
-#define SOT_WSORT_DPP 0x808E   /* bit m: the move from lane ^ m is a DPP (a VALU instruction) -- possible for m = 1, 2, 3, 7, 15; else a ds_swizzle (LDS crossbar) */
-#endif
-
-// Between two stages of the network the instruction scheduler may not move anything (1): a stage is 32 independent exchanges -- all the
-// parallelism a wave can use -- while a scheduler left free overlaps stages until it has used every register the occupancy target
-// allows (256 in the stand-alone kernel), and inlined into the row kernels that pushed THEIR long-lived values into scratch.
-#ifndef SOT_WSORT_GROUP
-#define SOT_WSORT_GROUP 8   /* registers per cross-lane group (moves in flight) */
-#endif
-#ifndef SOT_WSORT_TRANSPOSE_MIN
-#define SOT_WSORT_TRANSPOSE_MIN 4   /* merges whose largest lane distance S / 4 is at least this run their lane stages on the transposed layout (64: never) */
-#endif
-#ifndef SOT_WSORT_BUCKETS
-#define SOT_WSORT_BUCKETS 1   /* 32 keys per lane: the distribution form first, the network when a bucket overflows (0: the network always) */
-#endif
-#ifndef SOT_WSORT_ONE_REGION
-#define SOT_WSORT_ONE_REGION 1   /* the distribution form's counters and its image share their 8.25 KB of LDS (every base is read before a word is stored) */
-#endif
-#ifndef SOT_WSORT_FENCED
-#define SOT_WSORT_FENCED 1
-#endif
-#if SOT_WSORT_FENCED
-#define SOT_WSORT_STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define SOT_WSORT_STAGE_FENCE() do { } while (0)
-#endif
-
 namespace sot {
+
+// bit m: the move from lane ^ m is a DPP (a VALU instruction) -- possible for m = 1, 2, 3, 7, 15; else a ds_swizzle (LDS crossbar)
+constexpr uint32_t kWsortDpp = 0x808E;
+// Between two stages of the network the instruction scheduler may not move anything (sched_barrier): a stage is 32 independent exchanges --
+// all the parallelism a wave can use -- while a scheduler left free overlaps stages until it has used every register the occupancy target
+// allows (256 in the stand-alone kernel), and inlined into the row kernels that pushed THEIR long-lived values into scratch.
+constexpr int kWsortGroup = 8;           // registers per cross-lane group (moves in flight)
+constexpr int kWsortTransposeMin = 4;    // merges whose largest lane distance S / 4 is at least this run their lane stages on the transposed layout
 
 constexpr int kWaveSortRunLimit = 8;
 
 __host__ __device__ constexpr int wsort_ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 // LDS dwords the index / scratch array of a wave sort needs (the key array needs 64 KPL)
 // (64 KPL keys: the skewed image of 66 KPL dwords; with `buckets` KPL = 32 also holds the 2048 bucket counters of the distribution form behind it, skewed alike)
-__host__ __device__ constexpr int wave_sort_scratch(int kpl, bool buckets = false) { return ((kpl == 32 && buckets && !SOT_WSORT_ONE_REGION) ? 2 : 1) * (64 * kpl + 2 * kpl) + 2; }
+__host__ __device__ constexpr int wave_sort_scratch(int kpl) { return 64 * kpl + 2 * kpl + 2; }
 
 // ---------------------------------------------------------------------------------------------
 // Register <-> element maps.  VEC = false: register r of lane l is element (position) r 64 + l.  VEC = true (KPL % 4 == 0): element
@@ -74,11 +54,11 @@ template <int M>
 __device__ __forceinline__ uint32_t wsort_lane_xor(uint32_t v, uint32_t addr63)
 {
     (void)addr63;
-    if constexpr (((SOT_WSORT_DPP >> 1) & 1) && M == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
-    else if constexpr (((SOT_WSORT_DPP >> 2) & 1) && M == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
-    else if constexpr (((SOT_WSORT_DPP >> 3) & 1) && M == 3) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x1B, 0xF, 0xF, true);   // quad_perm [3,2,1,0]
-    else if constexpr (((SOT_WSORT_DPP >> 7) & 1) && M == 7) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);  // row_half_mirror
-    else if constexpr (((SOT_WSORT_DPP >> 15) & 1) && M == 15) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true); // row_mirror
+    if constexpr (((kWsortDpp >> 1) & 1) && M == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true);        // quad_perm [1,0,3,2]
+    else if constexpr (((kWsortDpp >> 2) & 1) && M == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
+    else if constexpr (((kWsortDpp >> 3) & 1) && M == 3) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x1B, 0xF, 0xF, true);   // quad_perm [3,2,1,0]
+    else if constexpr (((kWsortDpp >> 7) & 1) && M == 7) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true);  // row_half_mirror
+    else if constexpr (((kWsortDpp >> 15) & 1) && M == 15) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true); // row_mirror
     else if constexpr (M < 32) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x1F | (M << 10));                    // bit-mask mode: lane ^ M within 32
     else return (uint32_t)__builtin_amdgcn_ds_bpermute((int)addr63, (int)v);                                               // M == 63: addr63 = 4 (lane ^ 63)
 }
@@ -101,7 +81,7 @@ __device__ __forceinline__ void wsort_reg_tail(uint32_t (&w)[KPL])
                 w[r] = lo; w[r | J] = hi;
             }
         }
-        SOT_WSORT_STAGE_FENCE();
+        __builtin_amdgcn_sched_barrier(0);
         wsort_reg_tail<KPL, J / 2>(w);
     }
 }
@@ -126,18 +106,18 @@ __device__ __forceinline__ void wsort_reg_sort(uint32_t (&w)[KPL])
                     }
                 }
             }
-            SOT_WSORT_STAGE_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
 }
 
-// half cleaners between lanes at distances D, D / 2, ..., 1 (groups of SOT_WSORT_GROUP registers: that many moves in flight, no more
+// half cleaners between lanes at distances D, D / 2, ..., 1 (groups of kWsortGroup registers: that many moves in flight, no more
 // temporaries than that)
 template <int KPL, int D>
 __device__ __forceinline__ void wsort_lane_tail(uint32_t (&w)[KPL], int lane, uint32_t addr63)
 {
     if constexpr (D >= 1) {
-        constexpr int GRP = KPL < SOT_WSORT_GROUP ? KPL : SOT_WSORT_GROUP;
+        constexpr int GRP = KPL < kWsortGroup ? KPL : kWsortGroup;
         const uint32_t bound = (lane & D) ? 0xFFFFFFFFu : 0u;
 #pragma unroll
         for (int g = 0; g < KPL; g += GRP) {
@@ -146,7 +126,7 @@ __device__ __forceinline__ void wsort_lane_tail(uint32_t (&w)[KPL], int lane, ui
             for (int r = 0; r < GRP; ++r) t[r] = wsort_lane_xor<D>(w[g + r], addr63);
 #pragma unroll
             for (int r = 0; r < GRP; ++r) w[g + r] = wsort_med3(w[g + r], t[r], bound);
-            SOT_WSORT_STAGE_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
         }
         wsort_lane_tail<KPL, D / 2>(w, lane, addr63);
     }
@@ -168,7 +148,7 @@ __device__ __forceinline__ void wsort_transpose32(uint32_t (&w)[32], int lane, u
 #pragma unroll
     for (int r = 0; r < 32; ++r) w[r] = lds_ld_u32(crossed + 4u * 33u * (uint32_t)r);
     row_sync<1>();
-    SOT_WSORT_STAGE_FENCE();
+    __builtin_amdgcn_sched_barrier(0);
 }
 
 // merges across lanes: runs of (S / 2) KPL -> S KPL, S = 2 ... 64
@@ -177,7 +157,7 @@ __device__ __forceinline__ void wsort_lane_merges(uint32_t (&w)[KPL], int lane, 
 {
     if constexpr (S <= 64) {
         // flip: partner (lane ^ (S - 1), KPL - 1 - r); registers r and KPL - 1 - r only need each other: groups of pairs
-        constexpr int GRP = (KPL / 2 < SOT_WSORT_GROUP / 2) ? (KPL / 2 > 0 ? KPL / 2 : 1) : SOT_WSORT_GROUP / 2;
+        constexpr int GRP = (KPL / 2 < kWsortGroup / 2) ? (KPL / 2 > 0 ? KPL / 2 : 1) : kWsortGroup / 2;
         const uint32_t bound = (lane & (S / 2)) ? 0xFFFFFFFFu : 0u;
         if constexpr (KPL == 1) {
             w[0] = wsort_med3(w[0], wsort_lane_xor<S - 1>(w[0], addr63), bound);
@@ -189,10 +169,10 @@ __device__ __forceinline__ void wsort_lane_merges(uint32_t (&w)[KPL], int lane, 
                 for (int r = 0; r < GRP; ++r) { ta[r] = wsort_lane_xor<S - 1>(w[KPL - 1 - (g + r)], addr63); tb[r] = wsort_lane_xor<S - 1>(w[g + r], addr63); }
 #pragma unroll
                 for (int r = 0; r < GRP; ++r) { w[g + r] = wsort_med3(w[g + r], ta[r], bound); w[KPL - 1 - (g + r)] = wsort_med3(w[KPL - 1 - (g + r)], tb[r], bound); }
-                SOT_WSORT_STAGE_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if constexpr (KPL == 32 && S / 4 >= SOT_WSORT_TRANSPOSE_MIN) {
+        if constexpr (KPL == 32 && S / 4 >= kWsortTransposeMin) {
             // The half cleaners between lanes at distances S / 4 ... 1 (lane bits 4 ... 0) as exchanges between REGISTERS: the lane's low five
             // bits and the register index change places through the skewed LDS image (one store + one load per key each way, immediate
             // offsets, bank-conflict-free both ways), the stages run as one VALU instruction per key instead of a move + a v_med3, and the
@@ -274,7 +254,7 @@ __device__ __forceinline__ bool wsort_bucket_sort32(uint32_t (&w)[32], int lane,
 #pragma unroll
     for (int j = 0; j < 32; ++j) lds_st_u32(own + 4u * (uint32_t)j, c[j] + before);
     row_sync<1>();
-    // every word's position first (the bases are read before anything is stored): image and counters may then be ONE region (SOT_WSORT_ONE_REGION)
+    // every word's position first (the bases are read before anything is stored): image and counters are ONE region
 #pragma unroll
     for (int r = 0; r < 32; ++r) {
         const uint32_t base = lds_ld_u32(slot_of(w[r]));
@@ -339,7 +319,7 @@ __device__ __forceinline__ float wsort_wave_max(float v)
 // ---------------------------------------------------------------------------------------------
 // wave_sort_core: the same with the full keys behind a functor (keyof(i): the key of original element i -- LDS, or global memory when no
 // natural copy is kept) and WANT_KEYS = false for callers that only want the permutation (ok[] is then not written).
-template <int KPL, bool STORE_LDS, bool FULL, bool VEC, bool WANT_KEYS, bool BUCKETS = false, typename KeyOf>
+template <int KPL, bool STORE_LDS, bool FULL, bool VEC, bool WANT_KEYS, typename KeyOf>
 __device__ __forceinline__ bool wave_sort_core(const float (&x)[KPL], KeyOf keyof, float* key, uint32_t* idx, int n, int lane, float (&ok)[KPL], uint32_t (&oi)[KPL])
 {
     static_assert(!STORE_LDS || WANT_KEYS, "the natural-order stores need the sorted keys");
@@ -385,10 +365,9 @@ __device__ __forceinline__ bool wave_sort_core(const float (&x)[KPL], KeyOf keyo
         w[r] = full ? word : (word | pad_mask(r));   // every pad is the same word 0xFFFFFFFF: behind the data, never a run
     }
     bool placed = false;
-#if !defined(SOT_WSORT_DIAG_SKIP_NETWORK)   /* diagnostic (timing only, results are wrong): everything but the network */
-    if constexpr (KPL == 32 && BUCKETS && SOT_WSORT_BUCKETS) placed = wsort_bucket_sort32<FULL, VEC>(w, lane, n, lds_addr(idx), lds_addr(idx) + (SOT_WSORT_ONE_REGION ? 0u : 4u * 2112u));
+    // 32 keys per lane: the distribution form first (counters and image share one region), the network when a bucket overflows
+    if constexpr (KPL == 32) placed = wsort_bucket_sort32<FULL, VEC>(w, lane, n, lds_addr(idx), lds_addr(idx));
     if (!placed) wsort_network<KPL>(w, lane, lds_addr(idx));
-#endif
     // ---- neighbours that share q: (a ^ b) - 1 < MASK (a == b: two pads)
     uint32_t cmin = 0xFFFFFFFFu;
 #pragma unroll
@@ -471,7 +450,7 @@ __device__ __forceinline__ bool wave_sort_core(const float (&x)[KPL], KeyOf keyo
 template <int KPL, bool STORE_LDS = true, bool FULL = false, bool VEC = false>
 __device__ __forceinline__ bool wave_sort_kv(const float (&x)[KPL], float* key, uint32_t* idx, int n, int lane, float (&ok)[KPL], uint32_t (&oi)[KPL])
 {
-    return wave_sort_core<KPL, STORE_LDS, FULL, VEC, true, SOT_WSORT_ONE_REGION != 0>(x, [key](uint32_t i) { return key[i]; }, key, idx, n, lane, ok, oi);   // (one region: the scratch is no larger with the distribution form)
+    return wave_sort_core<KPL, STORE_LDS, FULL, VEC, true>(x, [key](uint32_t i) { return key[i]; }, key, idx, n, lane, ok, oi);
 }
 
 }  // namespace sot

@@ -57,7 +57,7 @@ def med3(a, b, c):
     return np.maximum(np.minimum(a, b), np.minimum(np.maximum(a, b), c))
 
 
-TRANSPOSE_MIN = 4        # sot_wave_sort.hpp: SOT_WSORT_TRANSPOSE_MIN
+TRANSPOSE_MIN = 4        # sot_wave_sort.hpp: kWsortTransposeMin
 
 
 def transpose32(w, count):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/ablate_libs/<name>.so = the product library with csrc/sot_stft.hip recompiled with extra flags:
-#   tools/build_stft_variant.sh nostore -DSOT_STFT_ABLATE_STORE=1
+#   tools/build_stft_variant.sh stftstamps -DSTFT_STAMPS
 set -e
 cd "$(dirname "$0")/.."
 name=$1; shift

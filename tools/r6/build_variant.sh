@@ -1,7 +1,7 @@
 #!/bin/bash
 # A diagnostic variant of the library: tools/ablate_libs/<name>.so = sot_hip.hip compiled as ONE object with the given SOT_PART mask
 # (missing families stubbed) + extra flags, linked with the product's stft / osc / mss objects.  Run with SOT_LIB_PATH=tools/ablate_libs/<name>.so.
-#   usage: tools/r6/build_variant.sh <name> <part mask> [flags...]        e.g.  tools/r6/build_variant.sh nowsort 18 -DSOT_WAVE_SORT=0
+#   usage: tools/r6/build_variant.sh <name> <part mask> [flags...]        e.g.  tools/r6/build_variant.sh stamps 18 -DSOT_STAMPS
 set -eu
 cd "$(dirname "$0")/../.."
 PKG=1d-spectral-optimal-transport_amd
