@@ -31,7 +31,7 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 13                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 14                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
 
 _vp = ctypes.c_void_p
@@ -70,6 +70,8 @@ EXPORTS = {
                                     _vp, _vp, ctypes.c_size_t, _vp]),
     "sot_w1d_quantiles": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp,
                                          ctypes.c_size_t, _vp]),
+    "sot_w1d_quantiles_backward": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  ctypes.c_size_t, _vp]),
     "sot_w1d_forward_csr": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_uint32, _vp, _vp]),
     "sot_segmented_sort": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp]),
@@ -582,7 +584,9 @@ def position_grads(x, y, xpos, ypos, p, flags, grad_row, need_x=True, need_y=Tru
     return out
 
 
-def quantiles(x, y, xpos, ypos, p, flags, plan=None):
+def quantiles(x, y, xpos, ypos, p, flags, plan=None, perm_out=None):
+    """The five return_quantiles tensors (sot_w1d_quantiles).  perm_out: a row_permutations() buffer the per-row sort leaves its
+    permutations in (for quantiles_backward)."""
     lib = load()
     dev = x.device
     B, n = x.shape
@@ -593,7 +597,7 @@ def quantiles(x, y, xpos, ypos, p, flags, plan=None):
     Q = torch.empty(B, K, dtype=torch.float32, device=dev)
     U = torch.empty(B, n, dtype=torch.float32, device=dev)
     V = torch.empty(B, m, dtype=torch.float32, device=dev)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_out)
     need_ws = _needs_workspace(pr, flags, plan)
     ws = workspace(pr, dev) if need_ws else None
     with _on_device(dev):
@@ -601,6 +605,38 @@ def quantiles(x, y, xpos, ypos, p, flags, plan=None):
                                    V.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
     check(rc, p)
     return uq, vq, Q, U, V
+
+
+def quantiles_backward(x, y, xpos, ypos, p, flags, grads, need, plan=None, perm_in=None):
+    """Vector-Jacobian product of quantiles() (sot_w1d_quantiles_backward).  grads: the upstream gradients of (uq, vq, Q, U, V), each a
+    [B, .] tensor or None; need: which of (grad_x, grad_y, grad_xpos, grad_ypos) to compute -- the others come back as None.  Position
+    gradients are per row for per-row positions and the batch sum [n] / [m] (sot_column_sum) for a shared position row, as
+    position_grads.  perm_in: the forward's row_permutations()."""
+    lib = load()
+    dev = x.device
+    B, n = x.shape
+    m = y.shape[1]
+    ups = []
+    for g, width in zip(grads, (n + m, n + m, n + m, n, m)):
+        if g is not None:
+            require_hip(g)
+            g = g.reshape(B, width).contiguous()
+        ups.append(g)
+    outs = [torch.empty(B, width, dtype=torch.float32, device=dev) if want else None for want, width in zip(need, (n, m, n, m))]
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_in=perm_in)
+    need_ws = _needs_workspace(pr, flags, plan)
+    ws = workspace(pr, dev) if need_ws else None
+    with _on_device(dev):
+        rc = lib.sot_w1d_quantiles_backward(ctypes.byref(pr), *[_ptr(g) for g in ups], *[_ptr(o) for o in outs], _ptr(ws),
+                                            ws.numel() if ws is not None else 0, stream_ptr(dev))
+        check(rc, p)
+        for k, pos, width in ((2, xpos, n), (3, ypos, m)):
+            if outs[k] is None or pos.ndim == 2:
+                continue
+            tot = torch.empty(width, dtype=torch.float32, device=dev)
+            check(lib.sot_column_sum(outs[k].data_ptr(), B, width, width, tot.data_ptr(), stream_ptr(dev)), p)
+            outs[k] = tot
+    return outs
 
 
 def forward_rows_csr(xw, xp, xoff, yw, yp, yoff, max_n, max_m, p, flags):

@@ -166,6 +166,41 @@ class _RowLoss(torch.autograd.Function):
         return gx, gy, gxp, gyp, None, None, None
 
 
+class _Quantiles(torch.autograd.Function):
+    """The five return_quantiles tensors (uq, vq, Q, U, V: losses.py:198-201, 299-300) with their vector-Jacobian product
+    (sot_w1d_quantiles_backward: one HIP kernel, one merge walk for weights and positions).  In the reference these tensors come from
+    plain ATen ops and stay attached to autograd -- they are its extension point for a ground cost other than |uq - vq|^p.  Per-row
+    positions are sorted once: the forward leaves the rows' permutations behind and the backward gathers through them, as in _RowLoss."""
+
+    @staticmethod
+    def forward(ctx, x, y, xpos, ypos, p, flags, plan):
+        perm = nat.row_permutations(x, y, xpos, ypos, flags) if plan is None else None
+        out = nat.quantiles(x, y, xpos, ypos, p, flags, plan, perm_out=perm)
+        ctx.save_for_backward(x, y, xpos, ypos, *([perm] if perm is not None else []))
+        ctx.p, ctx.flags, ctx.plan = p, flags, plan
+        ctx.set_materialize_grads(False)   # an output the caller's loss does not use arrives as None -> NULL: no traffic
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        x, y, xpos, ypos, *perm = ctx.saved_tensors
+        need = tuple(ctx.needs_input_grad[:4])
+        if all(g is None for g in grads):
+            return (None,) * 7
+        grads = [None if g is None else g.float() for g in grads]
+        gx, gy, gxp, gyp = nat.quantiles_backward(x, y, xpos, ypos, ctx.p, ctx.flags, grads, need, ctx.plan,
+                                                  perm_in=perm[0] if perm else None)
+        return gx, gy, gxp, gyp, None, None, None
+
+
+def _quantile_tensors(x, y, xpos, ypos, p, flags, plan):
+    """return_quantiles on the HIP route: through autograd when a gradient can be asked for, the plain native call otherwise."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)):
+        return _Quantiles.apply(x, y, xpos, ypos, p, flags, plan)
+    return nat.quantiles(x, y, xpos, ypos, p, flags, plan)
+
+
 EARLY_GRADIENT = True   # module switch for the loss-and-gradient form below (tests compare both forms)
 
 
@@ -302,7 +337,7 @@ def wasserstein_1d(u_values, v_values, u_weights=None, v_weights=None, p=1, requ
     flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
     plan = _functional_plans.get(upos, vpos) if (require_sort and upos.ndim == 1) else None
     if return_quantiles:
-        return nat.quantiles(x, y, upos, vpos, p, flags, plan)
+        return _quantile_tensors(x, y, upos, vpos, float(p), flags, plan)
     return _RowLoss.apply(x, y, upos, vpos, float(p), flags, plan)
 
 
@@ -510,7 +545,7 @@ class Wasserstein1D(torch.nn.Module):
     def _hip_forward(self, x, y, x_pos, y_pos, x_pos_, y_pos_, kwargs):
         if kwargs.get("return_quantiles", False):
             x2, y2, x_pos_, y_pos_, flags, plan, original_shape = self._marshal(x, y, x_pos, y_pos, kwargs)
-            out = nat.quantiles(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)
+            out = _quantile_tensors(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)
             return [t.reshape(original_shape + (-1,)) for t in out]
 
         original_shape = x.shape[:-1]

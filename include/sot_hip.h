@@ -27,8 +27,9 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 13   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
-                              * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned) */
+#define SOT_ABI_VERSION 14   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+                              * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
+                              *  14: sot_w1d_quantiles_backward) */
 
 typedef enum sot_status {
     SOT_OK = 0,
@@ -226,10 +227,40 @@ int sot_w1d_forward_csr(const float *x_weights, const float *x_positions, const 
 
 /*
  * return_quantiles=True (losses.py:198-201, 299-300): the five tensors the reference returns,
- * uq/vq/Q: [B, n+m], U: [B, n], V: [B, m]; any output pointer may be NULL.
+ * uq/vq/Q: [B, n+m], U: [B, n], V: [B, m]; any output pointer may be NULL.  Gradients: sot_w1d_quantiles_backward.
  */
 int sot_w1d_quantiles(const sot_problem *prob, float *uq, float *vq, float *Q, float *U, float *V,
                       void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Vector-Jacobian product of sot_w1d_quantiles (ABI 14): the five tensors are differentiable in the reference (losses.py:286-300 are
+ * sort, gather, cumsum, cat + sort, searchsorted, take_along_dim), and a caller who builds a ground cost of their own on them needs
+ * the gradients of the inputs.  Upstream gradients grad_uq / grad_vq / grad_Q [B, n+m], grad_U [B, n], grad_V [B, m], dense, each a
+ * device pointer or NULL (NULL = zero; an absent upstream costs no traffic).  Per row, with U, V the CDFs of the measures sorted by
+ * position (xs, ys), Q the merged levels and rank_U(q) = min(#{U_i < q}, n-1):
+ *   CDF entries:  GU_i = grad_U_i + grad_Q_k(i), GV_j = grad_V_j + grad_Q_k(j), k(.) the entry's place among the merged levels;
+ *   weights:      reverse cumulative sums of GU / GV (fp64), the normalisation term  g / M - [M > 1e-7] sum(g w) / M^2  (with
+ *                 SOT_FLAG_DONT_NORMALIZE the y term is folded into x's mass; none with SOT_FLAG_PRENORMALIZED), the factor 2 x of
+ *                 SOT_FLAG_SQUARE, back through the sort permutation -- the tail of sot_w1d_backward;
+ *   positions:    d / d xs[i] = sum_{k : rank_U(Q_k) = i} grad_uq_k, d / d ys[j] likewise with grad_vq, back through the sort
+ *                 permutation; the ranks themselves carry no gradient.
+ * Tie convention: the backward of `sort` hands grad_Q_k to the element of cat(U, V) at merged place k in stable order -- U before V,
+ * lower index first, as in sot_w1d_backward -- and a level inside a run of equal levels has the ranks of the run's first member
+ * (searchsorted side='left').
+ * Outputs grad_x / grad_xpos [B, n], grad_y / grad_ypos [B, m], dense, in the caller's original column order, each may be NULL (an
+ * absent output costs no traffic; all four NULL: SOT_OK, nothing is enqueued).  For a position row shared by all batch rows the
+ * caller sums grad_xpos / grad_ypos over the rows (sot_column_sum), as with sot_w1d_position_grad.  prob->p and SOT_FLAG_LIMIT_Q do
+ * not enter the result (the problem is validated as a whole all the same: p < 1 returns SOT_ERR_INVALID_P).  One kernel, one merge walk for weights and positions, deterministic (no atomics), enqueue-only, graph-capturable.
+ * Status as sot_w1d_backward: SOT_ERR_NULL_POINTER for prob == NULL, for a NULL x / y / xpos / ypos with B > 0 and for shared
+ * positions that still need their plan without a workspace; SOT_ERR_BAD_SHAPE for B < 0, n < 1, m < 1 or bad strides;
+ * SOT_ERR_INVALID_P; SOT_ERR_WORKSPACE; SOT_ERR_UNSUPPORTED_SIZE for rows past the gradient LDS budget, decided before anything is
+ * enqueued: the layout of sot_w1d_backward (n + m beyond ~13 000 on shared positions; per-row positions are laid out for the next
+ * powers of two, so pow2(n) + pow2(m) <= 12 000 always fits) plus, for rows too short to hold them in their own dead CDF region,
+ * 32 bytes per thread of the workgroup.
+ */
+int sot_w1d_quantiles_backward(const sot_problem *prob, const float *grad_uq, const float *grad_vq, const float *grad_Q,
+                               const float *grad_U, const float *grad_V, float *grad_x, float *grad_y, float *grad_xpos,
+                               float *grad_ypos, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Gradient of sum_r grad_scale * grad_row[r] * row_loss[r] w.r.t. the SUPPORT POSITIONS (losses.py:287-298 and 214-220: the positions
