@@ -31,8 +31,10 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 14                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 15                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
+FIR_TILE = 1024                  # include/sot_hip.h: SOT_FIR_TILE (outputs per workgroup of the FIR kernel)
+FIR_MIN_TAPS, FIR_MAX_TAPS, FIR_MAX_SAMPLES = 3, 512, 1 << 20   # the FIR kernels' domain (include/sot_hip.h: sot_fir_same_forward)
 
 _vp = ctypes.c_void_p
 
@@ -118,6 +120,11 @@ EXPORTS = {
                                                       ctypes.c_int, _vp, _vp, _vp]),
     "sot_stft_mag_backward_spec": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int,
                                                   _vp, _vp, _vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp]),
+    "sot_fir_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "sot_fir_same_forward": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                            _vp, _vp]),
+    "sot_fir_same_backward": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                             ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None
@@ -974,3 +981,63 @@ def synth_backward(amp_frames, freq_frames, window, n_samples, sample_rate, harm
                                      int(n_samples), float(sample_rate), grad_audio.data_ptr(), _ptr(ga), _ptr(gf), _ptr(tap_tables), ws.data_ptr(),
                                      ws.numel(), int(reuse), stream_ptr(dev)))
     return ga, gf
+
+
+def fir_in_domain(samples: int, n_taps: int, start: int) -> bool:
+    """The sizes sot_fir_same_forward / _backward take (include/sot_hip.h)."""
+    return 1 <= samples <= FIR_MAX_SAMPLES and FIR_MIN_TAPS <= n_taps <= FIR_MAX_TAPS and 0 <= start <= n_taps - 2
+
+
+def _fir_rows(audio: torch.Tensor, taps: torch.Tensor):
+    """(audio, its row stride, taps, their row stride -- 0 for one shared [n_taps] filter) as the library addresses them."""
+    require_hip(audio, taps)
+    if audio.ndim != 2 or taps.ndim not in (1, 2) or (taps.ndim == 2 and taps.shape[0] != audio.shape[0]):
+        raise RuntimeError("fir: expected audio [batch, samples] and taps [batch, n_taps] or [n_taps]")
+    audio = rows_view(audio)
+    batch, samples = audio.shape
+    if taps.ndim == 1:
+        taps, t_stride = taps.contiguous(), 0
+    else:
+        taps = rows_view(taps)
+        t_stride = taps.stride(0) if batch > 1 else taps.shape[1]
+    return audio, (audio.stride(0) if batch > 1 else samples), taps, t_stride
+
+
+def fir_same_forward(audio: torch.Tensor, taps: torch.Tensor, start: int) -> torch.Tensor:
+    """out[b,t] = sum_k taps[b,k] audio[b, t + start - k] (sot_fir_same_forward): audio [batch, samples] (unit inner stride, any row
+    stride >= samples), taps [batch, n_taps] or one shared [n_taps] filter -> [batch, samples]."""
+    lib = load()
+    audio, a_stride, taps, t_stride = _fir_rows(audio, taps)
+    batch, samples = audio.shape
+    out = torch.empty(batch, samples, dtype=torch.float32, device=audio.device)
+    with _on_device(audio.device):
+        check(lib.sot_fir_same_forward(audio.data_ptr(), a_stride, taps.data_ptr(), t_stride, batch, samples, taps.shape[-1], int(start),
+                                       out.data_ptr(), stream_ptr(audio.device)))
+    return out
+
+
+def fir_same_backward(grad_out: torch.Tensor, audio: torch.Tensor, taps: torch.Tensor, start: int, need_audio: bool = True,
+                      need_taps: bool = False):
+    """(grad_audio [batch, samples] or None, grad_taps or None) of fir_same_forward (sot_fir_same_backward).  grad_taps has the shape of
+    `taps`: for one shared filter the per-clip gradients are summed over the batch (sot_column_sum), which is what autograd's expand
+    backward returns."""
+    lib = load()
+    require_hip(grad_out)
+    audio, a_stride, taps, t_stride = _fir_rows(audio, taps)
+    batch, samples = audio.shape
+    n_taps = taps.shape[-1]
+    if tuple(grad_out.shape) != (batch, samples):
+        raise RuntimeError("fir_same_backward: grad_out must have the shape of the audio")
+    grad_out = grad_out.contiguous()
+    dev = audio.device
+    ga = torch.empty(batch, samples, dtype=torch.float32, device=dev) if need_audio else None
+    gt = torch.empty(batch, n_taps, dtype=torch.float32, device=dev) if need_taps else None
+    ws = torch.empty(max(8, int(lib.sot_fir_workspace_bytes(batch, samples, n_taps))), dtype=torch.uint8, device=dev) if need_taps else None
+    with _on_device(dev):
+        check(lib.sot_fir_same_backward(grad_out.data_ptr(), audio.data_ptr(), a_stride, taps.data_ptr(), t_stride, batch, samples, n_taps,
+                                        int(start), _ptr(ga), _ptr(gt), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev)))
+        if gt is not None and t_stride == 0:
+            tot = torch.empty(n_taps, dtype=torch.float32, device=dev)
+            check(lib.sot_column_sum(gt.data_ptr(), batch, n_taps, n_taps, tot.data_ptr(), stream_ptr(dev)))
+            gt = tot
+    return ga, gt

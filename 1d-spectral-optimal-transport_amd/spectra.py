@@ -307,11 +307,21 @@ class _Synth(torch.autograd.Function):
 
 
 def sinusoidal_synth(amplitudes: torch.Tensor, frequencies: torch.Tensor, n_samples: int, sample_rate: int = 16000,
-                     harmonic: bool = True) -> torch.Tensor:
+                     harmonic: bool = True, apply_roll_off: bool = False) -> torch.Tensor:
     """The reference's `synths.Sinusoidal(amp_scale_fn=None, freq_scale_fn=None)` (synths.py:43-128): frame-rate controls
     [batch, frames, sinusoids] (frequencies [batch, frames, 1] when `harmonic`: integer multiples of f0, ddsp.py:6-22) ->
     partials at or above Nyquist muted (ddsp.py:25-49) -> amplitudes upsampled with overlapping Hann windows, frequencies
-    linearly -> oscillator bank (the HIP kernels behind `oscillator_bank`; differentiable w.r.t. both controls)."""
+    linearly -> oscillator bank (the HIP kernels behind `oscillator_bank`; differentiable w.r.t. both controls).
+    apply_roll_off: the audio then goes through the -6 dB / octave roll-off above 500 Hz of synths.py:121-126 (the decoder of the paper's
+    MSS-LogLin runs): `frequency_filter` with the 128 taps of `roll_off_taps`, one filter shared by every clip, on every route."""
+    signal = _sinusoidal_signal(amplitudes, frequencies, n_samples, sample_rate, harmonic)
+    if apply_roll_off:
+        taps = roll_off_taps(signal.device)
+        signal = fft_convolve(signal, taps[None, :].expand(signal.shape[0], -1))
+    return signal
+
+
+def _sinusoidal_signal(amplitudes, frequencies, n_samples, sample_rate, harmonic):
     amplitudes, frequencies = amplitudes.float(), frequencies.float()
     if amplitudes.is_cuda and _envelope_kernels_apply(amplitudes, frequencies, n_samples, harmonic):
         if FUSED_SYNTH:
@@ -323,6 +333,183 @@ def sinusoidal_synth(amplitudes: torch.Tensor, frequencies: torch.Tensor, n_samp
         frequencies = frequencies * torch.linspace(1.0, float(k), k, device=frequencies.device)
     amplitudes = torch.where(frequencies >= sample_rate / 2.0, torch.zeros_like(amplitudes), amplitudes)
     return oscillator_bank(upsample_linear(frequencies, n_samples), upsample_window(amplitudes, n_samples), sample_rate)
+
+
+def slope_frequency_response(decay_per_octave_db, n_freqs, f_ref):
+    """The reference's `ddsp.slope_frequency_response` (ddsp.py:738-769): magnitudes [batch, frames, n_freqs] of a response that is 1 up to
+    `f_ref` and falls by `decay_per_octave_db` dB per octave above it, on `n_freqs` frequencies from 0 to 8000 Hz.  `decay_per_octave_db`
+    is a tensor ([batch, frames, 1], or 0-d); the frequency grid takes ITS dtype and device, as in the reference: the synthesiser's
+    `torch.tensor(6)` is int64, so its grid is the exact integers 0, 125, ... and the result (float32 by promotion, [1, 1, n_freqs]) is
+    exactly 1 up to 500 Hz.  Torch ops on a handful of values, differentiable w.r.t. a floating decay."""
+    decay = decay_per_octave_db
+    grid = torch.linspace(0, 8000, n_freqs).to(decay).reshape(1, 1, n_freqs)
+    grid[..., :1] = grid[..., :1] + 1e-7                       # keeps log2 away from 0 Hz; vanishes on an integer grid
+    per_octave = 10 ** (-decay / 20)                           # pressure factor of one octave
+    octaves = torch.log2(grid / f_ref)
+    return torch.where(grid > f_ref, per_octave ** octaves, torch.tensor(1.0).to(decay))
+
+
+def frequency_impulse_response(magnitudes: torch.Tensor, window_size: int = 0) -> torch.Tensor:
+    """The reference's `ddsp.frequency_impulse_response` (ddsp.py:382-482), the frequency-sampling design: one-sided magnitudes
+    [batch, n_freqs] or [batch, frames, n_freqs] -> zero-phase impulse response (irfft, 2 (n_freqs - 1) taps) -> times a Hann window of
+    `window_size` taps centred on tap 0 -> rotated into causal form.  window_size < 1 or beyond the response: the whole response (its
+    first tap is then the window's zero); a smaller window also crops the result: to window_size taps when odd, window_size - 1 when even.
+    Torch ops, differentiable."""
+    response = torch.fft.irfft(magnitudes, dim=-1)
+    framed = response.ndim == 3
+    if not framed:
+        response = response[:, None, :]
+    response = response.type(torch.float32)
+    size = int(response.shape[-1])
+    if window_size <= 0 or window_size > size:
+        window_size = size
+    window = torch.hann_window(window_size, device=response.device)
+    gap = size - window_size
+    if gap > 0:
+        half = (window_size + 1) // 2
+        # the window's second half at the front, its first half at the back, nothing in between
+        window = torch.cat([window[half:], torch.zeros(gap, device=response.device), window[:half]], dim=0)
+        response = window[None, None, :] * response
+        response = torch.cat([response[..., size - half + 2:], response[..., :half + 1]], dim=-1)
+    else:
+        window = torch.roll(window, shifts=window_size // 2, dims=-1)
+        response = torch.roll(window[None, None, :] * response, shifts=size // 2, dims=-1)
+    return response if framed else response[:, 0, :]
+
+
+def _fft_convolve_torch(audio, impulse_response, padding="same", delay_compensation=-1, cross_fade=False):
+    """`fft_convolve` on torch ops, in the reference's op order (ddsp.py:504-734): float32 casts, the audio cut into as many frames as the
+    impulse response has, both zero-padded to the next power of two >= frame + taps - 1, rfft, product, irfft, overlap-add (fold), crop.
+    The crop keeps the reference's arithmetic, oddities included: `start = (taps - 1) // 2 - 1` by default (two samples short of a
+    linear-phase filter's delay; -1 and an empty result for two taps), and for padding="valid" an end index that is wrong (empty when
+    frame + taps - 1 is a power of two).  cross_fade: the reference's branch cannot run (it hands `irfft` a tuple for `n`); this is what it
+    describes -- every frame also filtered with the PREVIOUS frame's response, the two mixed over the first taps - 1 samples with
+    sin^2 / cos^2 ramps."""
+    audio, impulse_response = audio.type(torch.float32), impulse_response.type(torch.float32)
+    if impulse_response.ndim == 2:
+        impulse_response = impulse_response[:, None, :]
+    ir_batch, n_frames, taps = impulse_response.shape
+    batch, samples = audio.shape
+    if batch != ir_batch:
+        raise ValueError(f"Batch size of audio ({batch}) and impulse response ({ir_batch}) must be the same.")
+    frame = -(-samples // n_frames)
+    pieces = list(torch.split(audio, frame, dim=-1))
+    if pieces[-1].shape[-1] < frame:
+        pieces[-1] = torch.nn.functional.pad(pieces[-1], (0, frame - pieces[-1].shape[-1]))
+    frames = torch.stack(pieces, dim=1)
+    if frames.shape[1] != n_frames:
+        raise ValueError(f"Number of audio frames ({frames.shape[1]}) and impulse response frames ({n_frames}) do not match: the number "
+                         "of impulse response frames must divide the audio into whole frames.")
+    fft_size = 1
+    while fft_size < frame + taps - 1:
+        fft_size *= 2
+    frames = torch.nn.functional.pad(frames, (0, fft_size - frame))
+    impulse_response = torch.nn.functional.pad(impulse_response, (0, fft_size - taps))
+    audio_spec = torch.fft.rfft(frames)
+    ir_spec = torch.fft.rfft(impulse_response)
+    filtered = torch.fft.irfft(audio_spec * ir_spec, n=fft_size)
+    if cross_fade:
+        previous = torch.fft.irfft(audio_spec * torch.roll(ir_spec, shifts=1, dims=1), n=fft_size)
+        overlap = taps - 1
+        ramp = torch.pi * torch.linspace(0, overlap, overlap, device=audio.device) / (2 * overlap)
+        fade_in, fade_out = torch.ones_like(filtered), torch.zeros_like(previous)
+        fade_in[:, 1:, :overlap] = torch.sin(ramp) ** 2      # the first frame has no predecessor to fade from
+        fade_out[:, 1:, :overlap] = torch.cos(ramp) ** 2
+        filtered = filtered * fade_in + previous * fade_out
+    total = (n_frames - 1) * frame + fft_size
+    out = torch.nn.functional.fold(filtered.transpose(1, 2), output_size=(1, total), kernel_size=(1, fft_size), stride=(1, frame))[:, 0, 0, :]
+    if padding == "valid":
+        keep = taps + samples - 1
+    elif padding == "same":
+        keep = samples
+    else:
+        raise ValueError(f"Padding must be 'valid' or 'same', instead of {padding}.")
+    start = (taps - 1) // 2 - 1 if delay_compensation < 0 else delay_compensation
+    end = (total - keep) - start
+    return out[:, start:-end]
+
+
+class _FirSame(torch.autograd.Function):
+    """sot_fir_same_forward / sot_fir_same_backward (include/sot_hip.h): taps [batch, n_taps], or one shared [n_taps] filter whose
+    gradient is the batch sum."""
+
+    @staticmethod
+    def forward(ctx, audio, taps, start):
+        from . import _native as nat
+        ctx.start = start
+        ctx.save_for_backward(audio if ctx.needs_input_grad[1] else None, taps)   # the audio is read by the tap gradient only
+        return nat.fir_same_forward(audio, taps, start)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import _native as nat
+        audio, taps = ctx.saved_tensors
+        need_audio, need_taps = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if audio is None:   # not kept (no tap gradient asked): the call then takes the shape from it and never reads it
+            audio = grad_out
+        grad_audio, grad_taps = nat.fir_same_backward(grad_out.float(), audio, taps, ctx.start, need_audio=need_audio, need_taps=need_taps)
+        return grad_audio, grad_taps, None
+
+
+def fft_convolve(audio: torch.Tensor, impulse_response: torch.Tensor, padding: str = "same", delay_compensation: int = -1,
+                 cross_fade: bool = False) -> torch.Tensor:
+    """The reference's `ddsp.fft_convolve` (ddsp.py:504-633): audio [batch, samples] filtered with an impulse response [batch, taps]
+    (time-invariant) or [batch, frames, taps] (one response per frame of the audio, overlap-added).  padding="same": the full convolution
+    cropped to `samples` outputs from sample `delay_compensation`, by default from (taps - 1) // 2 - 1 -- 62 for the 128 taps of
+    `frequency_impulse_response`, two short of their delay of 64, so the output is the zero-phase result delayed by two samples (kept:
+    it is what the reference's models were trained with).
+    float32 GPU tensors with a 2-D response, padding="same", no cross-fade, 3..512 taps, a crop start in [0, taps - 2] and up to 2^20
+    samples run the HIP FIR kernels as ONE autograd node (a direct fp32 sum per output; gradients w.r.t. audio and taps; a response
+    expanded over the batch is one shared filter).  Everything else -- CPU tensors, other dtypes, time-varying responses, cross_fade,
+    padding="valid", sizes outside that domain -- runs `_fft_convolve_torch`, the reference's FFT route on torch ops; a GPU tensor that
+    takes it says so once."""
+    if audio.is_cuda or impulse_response.is_cuda:
+        from . import _native as nat
+        taps = int(impulse_response.shape[-1])
+        start = (taps - 1) // 2 - 1 if delay_compensation < 0 else int(delay_compensation)
+        on_hip = (audio.is_cuda and impulse_response.is_cuda and audio.device == impulse_response.device and audio.dtype == torch.float32
+                  and impulse_response.dtype == torch.float32 and audio.ndim == 2 and impulse_response.ndim == 2
+                  and audio.shape[0] == impulse_response.shape[0] and audio.shape[0] >= 1 and padding == "same" and not cross_fade
+                  and nat.fir_in_domain(int(audio.shape[1]), taps, start))
+        if on_hip:
+            shared = impulse_response.shape[0] > 1 and impulse_response.stride(0) == 0
+            return _FirSame.apply(audio, impulse_response[0] if shared else impulse_response, start)
+        from .losses import warn_once
+        warn_once(("fft_convolve", padding, bool(cross_fade), impulse_response.ndim, str(audio.dtype), str(impulse_response.dtype), taps, start),
+                  f"fft_convolve: padding={padding!r}, cross_fade={cross_fade}, a {impulse_response.ndim}-D {impulse_response.dtype} response of "
+                  f"{taps} taps cropped from {start} on {audio.dtype} audio is outside what the HIP FIR kernels take (float32, 2-D response, "
+                  "padding='same', no cross-fade, 3..512 taps, 0 <= start <= taps - 2, up to 2^20 samples); running the FFT route on torch ops "
+                  "(rocFFT) instead")
+    return _fft_convolve_torch(audio, impulse_response, padding, delay_compensation, cross_fade)
+
+
+def frequency_filter(audio: torch.Tensor, magnitudes: torch.Tensor, window_size: int = 0, padding: str = "same",
+                     cross_fade: bool = False) -> torch.Tensor:
+    """The reference's `ddsp.frequency_filter` (ddsp.py:350-379): audio [batch, samples] through the linear-phase FIR filter that
+    `frequency_impulse_response` designs from the magnitudes [batch, n_freqs] (or [batch, frames, n_freqs]: time-varying).  Gradients
+    w.r.t. the magnitudes flow through the taps' torch ops.  Magnitudes expanded over the batch (stride 0, as the synthesiser's roll-off
+    passes them) are designed once and stay one shared filter."""
+    if magnitudes.ndim == 2 and magnitudes.shape[0] > 1 and magnitudes.stride(0) == 0:
+        taps = frequency_impulse_response(magnitudes[:1], window_size=window_size).expand(magnitudes.shape[0], -1)
+    else:
+        taps = frequency_impulse_response(magnitudes, window_size=window_size)
+    return fft_convolve(audio, taps, padding=padding, cross_fade=cross_fade)
+
+
+def roll_off_magnitudes(device) -> torch.Tensor:
+    """[1, 65] magnitudes of the synthesiser's harmonic roll-off (synths.py:122-123): -6 dB per octave above 500 Hz, from the int64 decay
+    the reference passes (see slope_frequency_response)."""
+    return slope_frequency_response(torch.tensor(6).to(device), n_freqs=65, f_ref=500)[0]
+
+
+_ROLL_OFF = _DeviceTableCache()
+
+
+def roll_off_taps(device) -> torch.Tensor:
+    """The 128 taps of the roll-off filter on `device` -- a constant, designed once per device (on that device, like the reference)."""
+    return _ROLL_OFF.get(("roll-off taps", str(device)), device, lambda: frequency_impulse_response(roll_off_magnitudes(device))[0],
+                         host_side=True)
 
 
 def harmonic_parameters(size: int, seed: int, n_sinusoids: int = 8, freq_min: float = 40.0, freq_max: float = 1950.0,

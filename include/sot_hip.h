@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 14   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+#define SOT_ABI_VERSION 15   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
                               * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
                               *  14: sot_w1d_quantiles_backward) */
 
@@ -432,6 +432,36 @@ int sot_mss_loss_and_grad(const float *target, int64_t target_row_stride, const 
                           float mag_weight, float logmag_weight, float eps, int l2, int per_clip, float post_scale,
                           float *loss /* [1] or [batch] */, float *grad_value /* [batch, samples] contiguous, or NULL */,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Time-invariant FIR filtering of [batch, samples] audio (ABI 15; csrc/sot_fir.hip): the reference's ddsp.fft_convolve for a 2-D
+ * impulse response (one frame) with padding="same" (ddsp.py:504-633, crop_and_compensate_delay :695-734) -- what frequency_filter
+ * (ddsp.py:350-379) runs and what synths.Sinusoidal(apply_roll_off=True) appends to its audio (synths.py:121-126: 128 taps) -- as a
+ * direct sum instead of a product of spectra.  With audio zero outside [0, samples):
+ *   out[b,t]        = sum_{k < n_taps} taps[b,k] * audio[b, t + start - k]                           0 <= t < samples
+ *   grad_audio[b,u] = sum_k taps[b,k] * grad_out[b, u - start + k]     (the same filter with reversed taps and start' = n_taps - 1 - start)
+ *   grad_taps[b,k]  = sum_t grad_out[b,t] * audio[b, t + start - k]
+ * start: the sample of the full linear convolution that becomes out[.,0].  The reference's default (delay_compensation < 0) is
+ *   (n_taps - 1) / 2 - 1 in integer division -- 62 for its 128 taps, NOT the filter's group delay of 64: its output keeps a delay of two
+ *   samples, and callers that want parity pass that value; a delay_compensation >= 0 is passed as it is.
+ * audio: rows audio_row_stride >= samples floats apart (a column slice of a wider tensor is fine); taps: [batch, n_taps] rows
+ *   taps_row_stride >= n_taps apart, or ONE filter for every clip with taps_row_stride == 0; out / grad_out / grad_audio: [batch, samples]
+ *   contiguous; grad_taps: [batch, n_taps] contiguous, per clip also for a shared filter (the caller sums the rows: sot_column_sum).
+ * sot_fir_same_backward: grad_audio and / or grad_taps may be NULL; `audio` is read for grad_taps only, `taps` for grad_audio only;
+ *   workspace (grad_taps only): sot_fir_workspace_bytes(batch, samples, n_taps) bytes on an 8-byte boundary (0 is returned outside the domain).
+ * Domain: float32, 3 <= n_taps <= 512, 0 <= start <= n_taps - 2, 1 <= samples <= 2^20 -- anything else SOT_ERR_UNSUPPORTED_SIZE (batch < 0,
+ *   samples < 1, n_taps < 1 or a row stride shorter than its row: SOT_ERR_BAD_SHAPE; SOT_ERR_NULL_POINTER; SOT_ERR_WORKSPACE), decided on
+ *   the host before anything is enqueued.  n_taps == 2 (the reference's default crop is -1 there and its result empty) and padding="valid"
+ *   (the reference's slice is broken) are outside on purpose.
+ * Numerics: every out / grad_audio element is ONE float32 fmaf chain over the taps in ascending order of the sum's own index, so a row's
+ *   bits do not depend on the batch or on tile boundaries; grad_taps: exact fp64 products added in t order, rounded once to float32.
+ * One workgroup per (clip, SOT_FIR_TILE consecutive outputs).  Deterministic (no atomics), enqueue-only, graph-capturable. */
+#define SOT_FIR_TILE 1024
+size_t sot_fir_workspace_bytes(int64_t batch, int64_t samples, int n_taps);
+int sot_fir_same_forward(const float *audio, int64_t audio_row_stride, const float *taps, int64_t taps_row_stride, int64_t batch,
+                         int64_t samples, int n_taps, int start, float *out, void *stream);
+int sot_fir_same_backward(const float *grad_out, const float *audio /* or NULL */, int64_t audio_row_stride, const float *taps /* or NULL */,
+                          int64_t taps_row_stride, int64_t batch, int64_t samples, int n_taps, int start, float *grad_audio /* or NULL */,
+                          float *grad_taps /* or NULL */, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
