@@ -31,12 +31,17 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 15                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 16                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
 FIR_TILE = 1024                  # include/sot_hip.h: SOT_FIR_TILE (outputs per workgroup of the FIR kernel)
 FIR_MIN_TAPS, FIR_MAX_TAPS, FIR_MAX_SAMPLES = 3, 512, 1 << 20   # the FIR kernels' domain (include/sot_hip.h: sot_fir_same_forward)
 
 _vp = ctypes.c_void_p
+
+
+class SotMetricGroup(ctypes.Structure):   # include/sot_hip.h: sot_metric_group
+    _fields_ = [("n_sizes", ctypes.c_int32), ("fft_sizes", ctypes.c_int32 * 8), ("mag_weight", ctypes.c_float), ("logmag_weight", ctypes.c_float),
+                ("lsd_weight", ctypes.c_float), ("l2", ctypes.c_int32)]
 
 
 class SotProblem(ctypes.Structure):
@@ -100,6 +105,9 @@ EXPORTS = {
     "sot_mss_loss_and_grad": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, ctypes.c_int,
                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp,
                                              ctypes.c_size_t, _vp]),
+    "sot_spec_metrics_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int]),
+    "sot_spec_metrics": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int,
+                                        ctypes.c_float, ctypes.c_int, _vp, _vp, ctypes.c_size_t, _vp]),
     "sot_spec_distance_workspace_bytes": (ctypes.c_size_t, []),
     "sot_spec_distance_forward": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int,
                                                  _vp, ctypes.c_int, _vp, ctypes.c_size_t, _vp]),
@@ -859,6 +867,43 @@ def mss_loss_and_grad(target: torch.Tensor, value: torch.Tensor, fft_sizes, wind
                                         float(eps), int(bool(l2)), int(bool(per_clip)), float(post_scale), loss.data_ptr(), _ptr(grad), ws.data_ptr(), ws.numel(),
                                         stream_ptr(value.device)))
     return loss, grad
+
+
+METRIC_MAX_GROUPS = 4   # include/sot_hip.h: SOT_METRIC_MAX_GROUPS
+
+
+def spec_metrics(target: torch.Tensor, value: torch.Tensor, fft_sizes, windows, groups, eps: float = 1e-5, per_clip: bool = False) -> torch.Tensor:
+    """Up to four metrics.ms_spectral_distance configurations (metrics.py:51-87) of [batch, samples] float32 audio in one pass of the fused
+    multi-scale engine (sot_spec_metrics) -> [groups], or [groups, batch] with per_clip.  fft_sizes / windows: the union of the groups' sizes,
+    each once, with one n_fft-tap device tensor per size; groups: (sizes, mag_weight, logmag_weight, lsd_weight, l2) tuples."""
+    require_hip(target, value)
+    lib = load()
+    if target.ndim != 2 or target.shape != value.shape:
+        raise RuntimeError("spec_metrics expects two [batch, samples] tensors of one shape")
+    target, value = rows_view(target), rows_view(value)
+    batch, samples = value.shape
+    t_stride = target.stride(0) if batch > 1 else samples
+    v_stride = value.stride(0) if batch > 1 else samples
+    n = len(fft_sizes)
+    sizes = (ctypes.c_int * n)(*[int(s) for s in fft_sizes])
+    wins = [_aligned8(w) for w in windows]
+    wptr = (ctypes.c_void_p * n)(*[w.data_ptr() for w in wins])
+    grp = (SotMetricGroup * max(1, len(groups)))()
+    for i, (gsizes, mag_w, log_w, lsd_w, l2) in enumerate(groups):
+        grp[i].n_sizes = len(gsizes)
+        for j, s in enumerate(list(gsizes)[:8]):
+            grp[i].fft_sizes[j] = int(s)
+        grp[i].mag_weight, grp[i].logmag_weight, grp[i].lsd_weight, grp[i].l2 = float(mag_w), float(log_w), float(lsd_w), int(bool(l2))
+    nbytes = int(lib.sot_spec_metrics_workspace_bytes(batch, samples, sizes, n, len(groups)))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=value.device)
+    out = torch.empty((len(groups), batch) if per_clip else (len(groups),), dtype=torch.float32, device=value.device)
+    if batch == 0:   # nothing is launched: the mean over an empty batch is NaN (torch.mean of nothing)
+        out.fill_(float("nan"))
+    with _on_device(value.device):
+        check(lib.sot_spec_metrics(target.data_ptr(), t_stride, value.data_ptr(), v_stride, batch, samples, ctypes.cast(sizes, ctypes.c_void_p),
+                                   ctypes.cast(wptr, ctypes.c_void_p), n, ctypes.cast(grp, ctypes.c_void_p), len(groups), float(eps), int(bool(per_clip)),
+                                   out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(value.device)))
+    return out
 
 
 def oscillator_bank_forward(freq: torch.Tensor, amp: torch.Tensor, sample_rate: float, return_workspace: bool = False):

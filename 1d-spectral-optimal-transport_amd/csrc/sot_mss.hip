@@ -68,6 +68,24 @@ struct MssArgs {
     float* loss; float* grad;                         // outputs: [1] or [batch]; [batch, samples] (contiguous)
 };
 
+// Metric mode (KIND 2, forward only; include/sot_hip.h: sot_spec_metrics): up to kMaxGroups calls of the reference's metrics.ms_spectral_distance
+// (metrics.py:51-87) in one pass over the UNION of their FFT sizes -- the scales of MssArgs are that union; a group is a subset of them in an
+// order of its own, three weights and L1 / L2.  A task's group membership depends on its scale alone: every branch on it is scalar.
+constexpr int kMaxGroups = 4;
+constexpr int kNeedLog = 1 << 8, kNeedLsd = 1 << 9;   // bits of scale_mask above the group bits
+struct MetArgs : MssArgs {
+    int n_groups;
+    int scale_mask[kMaxScales];                       // bit g: group g holds the scale; kNeedLog / kNeedLsd: one of those groups has a log-magnitude / an LSD term
+    double g_mag[kMaxGroups], g_logmag[kMaxGroups], g_lsd[kMaxGroups];   // the float32 weights as doubles: scalar operands of the double products (converted in
+                                                      // the kernel they would be uniform values in vector register pairs, 24 of them)
+    int g_l2[kMaxGroups];
+    int g_plain[kMaxGroups];                          // L1 on the magnitudes and nothing else: float32 lane sums, the arithmetic of KIND 0
+    int g_sizes[kMaxGroups], g_scale[kMaxGroups][kMaxScales];   // the group's scales (indices into the union) in ITS order: the order of `loss +=`
+    double* partial;                                  // [group][task]; written for the groups of the task's scale only
+    float* out;                                       // [n_groups] or [n_groups, batch]
+};
+struct MetAcc { int mask; float f[kMaxGroups]; double d[kMaxGroups]; };
+
 __device__ __forceinline__ float safe_logf(float x, float eps) { return logf(x <= eps ? eps : x); }
 
 // range test of a frame's windowed samples (csrc/sot_stft.hip: frame_is_plain): then re^2 + im^2 of its bins neither overflows nor loses the bins that matter
@@ -97,6 +115,30 @@ __device__ __forceinline__ float bin_term(const MssArgs& a, float t, float v, do
         gv -= (v <= a.eps) ? 0.0f : a.logmag_weight * g / v;    // where(x <= eps, eps, x): no gradient below eps
     }
     return gv;
+}
+
+// one bin in metric mode: the three differences once, then every group of the task's scale takes its terms (scalar branches).  The magnitude
+// and log-magnitude terms are those of bin_term (a `plain` group: those of KIND 0), so a group without LSD weight has the bits of the loss
+// engine; the LSD term is d = 10 log10(max(t t, eps)) - 10 log10(max(v v, eps)), the square rounded to float32 first as `target_mag**2`
+// is (metrics.py:82-85, utils.py:154-157), with the accurate log10f: the difference of two nearby logarithms magnifies an absolute error.
+__device__ __forceinline__ void metric_bin(const MetArgs& a, float t, float v, MetAcc& c)
+{
+    const float dm = t - v;
+    float dl = 0.0f, dd = 0.0f;
+    if (c.mask & kNeedLog) dl = safe_logf(t, a.eps) - safe_logf(v, a.eps);
+    if (c.mask & kNeedLsd) {
+        const float tt = t * t, vv = v * v;
+        dd = 10.0f * log10f(tt <= a.eps ? a.eps : tt) - 10.0f * log10f(vv <= a.eps ? a.eps : vv);
+    }
+#pragma unroll
+    for (int g = 0; g < kMaxGroups; ++g) {
+        if (!((c.mask >> g) & 1)) continue;
+        if (a.g_plain[g]) { c.f[g] += fabsf(dm); continue; }
+        const bool l2 = a.g_l2[g] != 0;
+        if (a.g_mag[g] > 0.0) c.d[g] += a.g_mag[g] * (l2 ? (double)(dm * dm) : (double)fabsf(dm));
+        if (a.g_logmag[g] > 0.0) c.d[g] += a.g_logmag[g] * (l2 ? (double)(dl * dl) : (double)fabsf(dl));
+        if (a.g_lsd[g] > 0.0) c.d[g] += a.g_lsd[g] * (l2 ? (double)(dd * dd) : (double)fabsf(dd));
+    }
 }
 
 // frames [frame0, frame0 + F) of one signal: raw packed points (samples 2 i, 2 i + 1) and the window's tap pairs into registers -- loads only,
@@ -158,10 +200,11 @@ __device__ __forceinline__ void window_frames(v2f (&rt)[16], v2f (&rv)[16], cons
 //   s = H_k + conj H_(m-k), P = i conj(W) (H_k - conj H_(m-k)):   G_k = s + P,   G_(m-k) = conj(s - P)     (csrc/sot_stft.hip, backward).
 // KIND 0: the paper's distance (L1 on the magnitudes only: mag_weight |t - v|, float32 partial sums per lane); KIND 1: every combination
 // (L1 / L2, magnitudes and / or their safe_log; float64 partial sums).  PLAIN: the frame passed the range test: |x| = v_sqrt(re^2 + im^2),
-// 1 / |x| = v_rsq; otherwise hypotf and an IEEE division.
+// 1 / |x| = v_rsq; otherwise hypotf and an IEEE division.  KIND 2: the metric mode (`a` is a MetArgs; the sums go to `mc`, see metric_bin).
 template <int M, bool PLAIN, bool SECOND, bool GRAD, int KIND>
-__device__ __forceinline__ void pair_pass(const MssArgs& a, float coef, v2f* zl, const v2f* wn, int lane, float (&tm)[18], float& accf, double& acc)
+__device__ __forceinline__ void pair_pass(const MssArgs& a, float coef, v2f* zl, const v2f* wn, int lane, float (&tm)[18], float& accf, double& acc, MetAcc& mc)
 {
+    static_assert(KIND != 2 || !GRAD, "the metric mode is forward only");
     using G = Geo<M>;
     const int j = lane >> G::logL, l = lane & (G::L - 1);
     v2f* const pk = zl + j * (G::m + G::L) + l;         // + L q
@@ -191,6 +234,11 @@ __device__ __forceinline__ void pair_pass(const MssArgs& a, float coef, v2f* zl,
             if (q < 8) accf += fabsf(dm);                 // k = m / 2 (q = 8) is its own partner: one bin; k = 0 pairs with bin m
             gk = dk > 0.0f ? -cw : cw; gk = dk == 0.0f ? 0.0f : gk;    // torch: sgn(0) = 0
             gm = dm > 0.0f ? -cw : cw; gm = dm == 0.0f ? 0.0f : gm;
+        } else if (KIND == 2) {
+            const MetArgs& ma = static_cast<const MetArgs&>(a);
+            metric_bin(ma, tm[2 * q], mk, mc);
+            if (q < 8) metric_bin(ma, tm[2 * q + 1], mm, mc);
+            gk = gm = 0.0f;
         } else {
             gk = coef * bin_term(a, tm[2 * q], mk, acc);
             gm = (q < 8) ? coef * bin_term(a, tm[2 * q + 1], mm, acc) : 0.0f;
@@ -250,6 +298,7 @@ __device__ __forceinline__ void wave_task(const MssArgs& a, int s, int task, con
     float tm[18];
     float accf = 0.0f;
     double acc = 0.0;
+    MetAcc mc = {};                                               // KIND 2 only (zeroed below, after the transforms: nothing of it is live across them)
     v2f r[16], rv[16];
     // ---- both signals' frames and the taps in one round of loads; the estimate's windowed frames wait in registers
     fetch_frames<M>(tclip, a.samples, frames, frame0, win, lane, r);
@@ -262,8 +311,8 @@ __device__ __forceinline__ void wave_task(const MssArgs& a, int s, int task, con
     MSS_STAMP(3);
     write_natural<M>(r, zl, lane);
     wave_sync();
-    if (plain) pair_pass<M, true, false, false, KIND>(a, 0.0f, zl, wn, lane, tm, accf, acc);
-    else pair_pass<M, false, false, false, KIND>(a, 0.0f, zl, wn, lane, tm, accf, acc);
+    if (plain) pair_pass<M, true, false, false, KIND>(a, 0.0f, zl, wn, lane, tm, accf, acc, mc);
+    else pair_pass<M, false, false, false, KIND>(a, 0.0f, zl, wn, lane, tm, accf, acc, mc);
     wave_sync();
     MSS_STAMP(4);
     // ---- estimate: |V|, distance, gradient packing
@@ -272,15 +321,32 @@ __device__ __forceinline__ void wave_task(const MssArgs& a, int s, int task, con
     write_natural<M>(rv, zl, lane);
     wave_sync();
     const float coef = a.coef[s];
-    if (plain_v) pair_pass<M, true, true, GRAD, KIND>(a, coef, zl, wn, lane, tm, accf, acc);
-    else pair_pass<M, false, true, GRAD, KIND>(a, coef, zl, wn, lane, tm, accf, acc);
+    if (KIND == 2) {
+        mc = MetAcc{};
+        mc.mask = static_cast<const MetArgs&>(a).scale_mask[s];
+    }
+    if (plain_v) pair_pass<M, true, true, GRAD, KIND>(a, coef, zl, wn, lane, tm, accf, acc, mc);
+    else pair_pass<M, false, true, GRAD, KIND>(a, coef, zl, wn, lane, tm, accf, acc, mc);
     wave_sync();
     MSS_STAMP(6);
     // ---- the task's distance sum: lanes -> wave (fixed shuffle tree)
-    if (KIND == 0) acc = (double)accf * (double)a.mag_weight;
+    if constexpr (KIND == 2) {                                    // one sum per group of the scale, each by the same tree
+        const MetArgs& ma = static_cast<const MetArgs&>(a);
+        const int64_t total = a.task_base[a.n_scales];
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
-    if (lane == 0) a.partial_loss[task] = acc;
+        for (int g = 0; g < kMaxGroups; ++g) {
+            if (!((mc.mask >> g) & 1)) continue;
+            double sum = ma.g_plain[g] ? (double)mc.f[g] * ma.g_mag[g] : mc.d[g];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+            if (lane == 0) ma.partial[g * total + task] = sum;
+        }
+    } else {
+        if (KIND == 0) acc = (double)accf * (double)a.mag_weight;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+        if (lane == 0) a.partial_loss[task] = acc;
+    }
     if (GRAD) {
         // ---- inverse: G (natural order) -> last-phase registers -> time order; windowed, scaled frame gradients
         const int j = lane >> G::logL, kl = lane & (G::L - 1);
@@ -498,6 +564,84 @@ __global__ __launch_bounds__(kFinishThreads) void mss_finish_kernel(const MssArg
     }
 }
 
+// The metric mode of the engine: the same persistent grid and task order, GRAD = false, KIND = 2 (one more kernel, not a third KIND of
+// mss_fused_kernel's argument type: the training instantiations and their names stay as they are).
+template <int kWaves>
+__global__ __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(kWavesPerEu, kWavesPerEu))) void mss_metric_kernel(const MetArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem_f[];
+    v2f* const tw = reinterpret_cast<v2f*>(smem_f);
+    v2f* const wn = tw + kTw;
+    v2f* const bufs = wn + kWnMax;
+    build_tables<64 * kWaves>(kWn, tw, wn);
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    v2f* const zl = bufs + wave * kBuf;
+    const int total = a.task_base[a.n_scales];
+    const int stride = (int)gridDim.x * kWaves;
+    int s = 0;
+    for (int task = (int)blockIdx.x * kWaves + wave; task < total; task += stride) {
+        while (s + 1 < a.n_scales && task >= a.task_base[s + 1]) ++s;
+        switch (a.logm[s]) {
+            case 5: wave_task<5, false, 2>(a, s, task, tw, wn, zl); break;
+            case 6: wave_task<6, false, 2>(a, s, task, tw, wn, zl); break;
+            case 7: wave_task<7, false, 2>(a, s, task, tw, wn, zl); break;
+            case 8: wave_task<8, false, 2>(a, s, task, tw, wn, zl); break;
+            case 9: wave_task<9, false, 2>(a, s, task, tw, wn, zl); break;
+            default: wave_task<10, false, 2>(a, s, task, tw, wn, zl); break;
+        }
+    }
+}
+
+// Finish of the metric mode: group g = blockIdx.y.  Per scale of the group, in the group's order: the task partials in the fixed order of
+// mss_finish_kernel (thread t adds partials t, t + 256, ...; shuffle tree; the four wave sums in order), times 1 / count, rounded to float32,
+// `loss += mean` in float32 (metrics.py:66-85).  per_clip: a thread per clip, its tasks in order.
+__global__ __launch_bounds__(kFinishThreads) void metric_finish_kernel(const MetArgs a)
+{
+    __shared__ double red[kFinishThreads / 64];
+    const int g = (int)blockIdx.y;
+    const double* const part = a.partial + (int64_t)g * a.task_base[a.n_scales];
+    const int sizes = a.g_sizes[g];
+    if (a.per_clip) {
+        for (int64_t o = (int64_t)blockIdx.x * kFinishThreads + threadIdx.x; o < a.batch; o += (int64_t)gridDim.x * kFinishThreads) {
+            float total = 0.0f;
+            for (int i = 0; i < sizes; ++i) {
+                const int s = a.g_scale[g][i];
+                double acc = 0.0;
+                for (int c = 0; c < a.waves[s]; ++c) acc += part[a.task_base[s] + o * a.waves[s] + c];
+                total += (float)(acc * a.inv_count[s]);
+            }
+            a.out[(int64_t)g * a.batch + o] = total;
+        }
+        return;
+    }
+    float total = 0.0f;
+    for (int i = 0; i < sizes; ++i) {
+        const int s = a.g_scale[g][i];
+        const int count = a.task_base[s + 1] - a.task_base[s];
+        const double* const src = part + a.task_base[s];
+        double acc = 0.0;
+        for (int i0 = 0; i0 < count; i0 += kLossLoads * kFinishThreads) {
+            double p[kLossLoads];
+#pragma unroll
+            for (int u = 0; u < kLossLoads; ++u) p[u] = src[min(i0 + u * kFinishThreads + (int)threadIdx.x, count - 1)];     // all in flight together
+#pragma unroll
+            for (int u = 0; u < kLossLoads; ++u) acc += (i0 + u * kFinishThreads + (int)threadIdx.x < count) ? p[u] : 0.0;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        double tot = 0.0;
+#pragma unroll
+        for (int w = 0; w < kFinishThreads / 64; ++w) tot += red[w];
+        tot *= a.inv_count[s];
+        total += (float)tot;
+        __syncthreads();      // red[] is free for the next scale
+    }
+    if (threadIdx.x == 0) a.out[g] = total;
+}
+
 static int fill(const float* target, int64_t stride_t, const float* value, int64_t stride_v, int64_t batch, int64_t samples, const int* fft_sizes,
                 const float* const* windows, int n_scales, float mag_weight, float logmag_weight, float eps, int l2, int per_clip, MssArgs* a,
                 size_t* workspace_bytes, size_t* grad_offset_bytes)
@@ -603,6 +747,115 @@ int sot_mss_loss_and_grad(const float* target, int64_t target_row_stride, const 
     const int64_t work = a.want_grad ? (batch * ((((samples + 1) / 2) + 255) / 256) + 1) / 2 : 1;      // one workgroup per TWO (clip, 256 packed points) blocks
     const int64_t blocks = (work < 16384 ? (work < 1 ? 1 : work) : 16384) + ((a.want_grad && !per_clip) ? 1 : 0);      // + the loss workgroup
     hipLaunchKernelGGL(mss_finish_kernel, dim3((unsigned)blocks), dim3(kFinishThreads), 0, st, a);
+    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+}
+
+}  // extern "C"
+
+// ---- the metric mode's entry points (include/sot_hip.h)
+namespace sot_mss {
+
+// the union's scales through fill() (the workspace it sizes is the loss engine's: not used here), then the groups
+static int fill_metrics(const float* target, int64_t stride_t, const float* value, int64_t stride_v, int64_t batch, int64_t samples, const int* fft_sizes,
+                        const float* const* windows, int n_sizes, const sot_metric_group* groups, int n_groups, float eps, int per_clip, MetArgs* a,
+                        size_t* workspace_bytes)
+{
+    if (n_groups < 1 || n_groups > kMaxGroups || n_sizes < 1 || n_sizes > kMaxScales) return SOT_ERR_BAD_SHAPE;
+    size_t unused = 0, unused2 = 0;
+    const int rc = fill(target, stride_t, value, stride_v, batch, samples, fft_sizes, windows, n_sizes, 1.0f, 0.0f, eps, 0, per_clip, a, &unused, &unused2);
+    if (rc != SOT_OK) return rc;
+    for (int s = 0; s < n_sizes; ++s)
+        for (int u = 0; u < s; ++u)
+            if (fft_sizes[u] == fft_sizes[s]) return SOT_ERR_BAD_SHAPE;      // the union names every size once
+    a->n_groups = n_groups;
+    for (int g = 0; g < n_groups; ++g) {
+        const sot_metric_group& grp = groups[g];
+        const bool mag = grp.mag_weight > 0.0f, lg = grp.logmag_weight > 0.0f, lsd = grp.lsd_weight > 0.0f;
+        if (grp.n_sizes < 1 || grp.n_sizes > kMaxScales || !(mag || lg || lsd)) return SOT_ERR_BAD_SHAPE;
+        a->g_mag[g] = (double)grp.mag_weight; a->g_logmag[g] = (double)grp.logmag_weight; a->g_lsd[g] = (double)grp.lsd_weight;
+        a->g_l2[g] = grp.l2 != 0;
+        a->g_plain[g] = mag && !lg && !lsd && grp.l2 == 0;
+        a->g_sizes[g] = grp.n_sizes;
+        for (int i = 0; i < grp.n_sizes; ++i) {
+            const int n = grp.fft_sizes[i];
+            if (n < 64 || n > 2048 || (n & (n - 1)) != 0) return SOT_ERR_UNSUPPORTED_SIZE;
+            int s = 0;
+            while (s < n_sizes && fft_sizes[s] != n) ++s;
+            if (s == n_sizes) return SOT_ERR_BAD_SHAPE;                      // not in the union
+            a->g_scale[g][i] = s;
+            a->scale_mask[s] |= (1 << g) | (lg ? kNeedLog : 0) | (lsd ? kNeedLsd : 0);
+        }
+    }
+    *workspace_bytes = sizeof(double) * (size_t)n_groups * (size_t)a->task_base[n_sizes];
+    return SOT_OK;
+}
+
+// The dynamic-LDS opt-in of one kernel: its own state per kernel instantiation (a static of this template), per device; idempotent, a benign
+// race sets it twice.
+template <int kWaves>
+static void metric_lds_opt_in(int dev)
+{
+    static bool done[64] = {};
+    if (dev >= 0 && dev < 64 && done[dev]) return;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mss_metric_kernel<kWaves>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kWaves)) != hipSuccess)
+        (void)hipGetLastError();
+    if (dev >= 0 && dev < 64) done[dev] = true;
+}
+
+}  // namespace sot_mss
+
+extern "C" {
+
+size_t sot_spec_metrics_workspace_bytes(int64_t batch, int64_t samples, const int* fft_sizes, int n_sizes, int n_groups)
+{
+    using namespace sot_mss;
+    if (fft_sizes == nullptr || n_groups < 1 || n_groups > kMaxGroups || n_sizes < 1 || n_sizes > kMaxScales) return 0;
+    MetArgs a{};
+    size_t bytes = 0, off = 0;
+    if (fill(nullptr, samples, nullptr, samples, batch, samples, fft_sizes, nullptr, n_sizes, 1.0f, 0.0f, 1e-5f, 0, 0, &a, &bytes, &off) != SOT_OK) return 0;
+    return sizeof(double) * (size_t)n_groups * (size_t)a.task_base[n_sizes];
+}
+
+int sot_spec_metrics(const float* target, int64_t target_row_stride, const float* value, int64_t value_row_stride, int64_t batch, int64_t samples,
+                     const int* fft_sizes, const float* const* windows, int n_sizes, const sot_metric_group* groups, int n_groups, float eps,
+                     int per_clip, float* out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    using namespace sot_mss;
+    if (fft_sizes == nullptr || windows == nullptr || groups == nullptr) return SOT_ERR_NULL_POINTER;
+    MetArgs a{};
+    size_t need = 0;
+    const int rc = fill_metrics(target, target_row_stride, value, value_row_stride, batch, samples, fft_sizes, windows, n_sizes, groups, n_groups, eps,
+                                per_clip, &a, &need);
+    if (rc != SOT_OK) return rc;
+    if (batch == 0) return SOT_OK;
+    if (target == nullptr || value == nullptr || out == nullptr || workspace == nullptr) return SOT_ERR_NULL_POINTER;
+    if (workspace_bytes < need) return SOT_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0) return SOT_ERR_BAD_SHAPE;
+    a.partial = reinterpret_cast<double*>(workspace);
+    a.out = out;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    (void)hipGetLastError();
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    int cus = 256;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
+    // the engine's two grid forms (sot_mss_loss_and_grad): 4-wave workgroups for one round of 16 x CUs wave slots, 16-wave workgroups beyond
+    const int tasks = a.task_base[n_sizes], slots = 16 * cus;
+    const bool small = tasks <= slots;
+    const int wg_waves = small ? 4 : 16;
+    const int waves_needed = tasks < slots ? tasks : slots;
+    const dim3 grid((unsigned)((waves_needed + wg_waves - 1) / wg_waves));
+    if (small) {
+        metric_lds_opt_in<4>(dev);
+        hipLaunchKernelGGL(mss_metric_kernel<4>, grid, dim3(64 * 4), lds_bytes(4), st, a);
+    } else {
+        metric_lds_opt_in<16>(dev);
+        hipLaunchKernelGGL(mss_metric_kernel<16>, grid, dim3(64 * 16), lds_bytes(16), st, a);
+    }
+    if (hipGetLastError() != hipSuccess) return SOT_ERR_LAUNCH;
+    const int64_t clip_blocks = (batch + kFinishThreads - 1) / kFinishThreads;
+    const unsigned fx = per_clip ? (unsigned)(clip_blocks < 4096 ? clip_blocks : 4096) : 1u;
+    hipLaunchKernelGGL(metric_finish_kernel, dim3(fx, (unsigned)n_groups), dim3(kFinishThreads), 0, st, a);
     return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
 }
 

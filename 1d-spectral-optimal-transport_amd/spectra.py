@@ -47,7 +47,13 @@ class _DeviceTableCache:
 
     def get(self, key, device, make, host_side=False):
         """host_side: `make` copies host data to the device (cannot happen inside a capture: the caller must have used the
-        table once outside it, as any warm-up step does)."""
+        table once outside it, as any warm-up step does).  A table is always an ordinary tensor, also when the first caller runs under
+        torch.inference_mode() (the evaluation metrics do): an inference tensor in the cache could not be saved for backward by the
+        training step that asks for the same table later."""
+        with torch.inference_mode(False):
+            return self._get(key, device, make, host_side)
+
+    def _get(self, key, device, make, host_side):
         hit = self.entries.get(key)
         if hit is not None:
             table, ready, stream = hit

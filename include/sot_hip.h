@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 15   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+#define SOT_ABI_VERSION 16   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
                               * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
-                              *  14: sot_w1d_quantiles_backward) */
+                              *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics) */
 
 typedef enum sot_status {
     SOT_OK = 0,
@@ -432,6 +432,35 @@ int sot_mss_loss_and_grad(const float *target, int64_t target_row_stride, const 
                           float mag_weight, float logmag_weight, float eps, int l2, int per_clip, float post_scale,
                           float *loss /* [1] or [batch] */, float *grad_value /* [batch, samples] contiguous, or NULL */,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Evaluation metrics on the same engine (ABI 16; csrc/sot_mss.hip, metric mode): up to SOT_METRIC_MAX_GROUPS calls of the reference's
+ * metrics.ms_spectral_distance (metrics.py:51-87) on the same two signals in ONE pass, forward only.  A group is one such call:
+ *   out[g] = sum over the group's sizes, in the group's order, of the float32 mean over the scale's bins of
+ *            mag_weight * D(t - v) + logmag_weight * D(slog t - slog v) + lsd_weight * D(10 log10 max'(t t) - 10 log10 max'(v v)),
+ *   t = |T_k|, v = |V_k| as sot_mss_loss_and_grad forms them, D = |.| (l2 == 0) or (.)^2, slog(x) = log(max'(x)), max'(x) = (x <= eps ? eps : x)
+ *   (utils.py:145-157; the squares are rounded to float32 first; both logarithms are the accurate libm ones).  A weight <= 0 switches its term off.
+ * fft_sizes[n_sizes] / windows: the UNION of the groups' sizes, each once, n_sizes <= 8, powers of two in [64, 2048], hop = n_fft / 4; every
+ * audio sample is fetched and every frame transformed once per size of the union, however many groups name the size.  A group names sizes of
+ * the union (its own order; that is the order of the float32 `loss +=`).  per_clip != 0: the means run over each clip's own spectrogram.
+ * out: [n_groups], or [n_groups, batch] with per_clip.  A group without lsd_weight has the bits of sot_mss_loss_and_grad's loss for the same
+ * sizes and weights (same engine, same summation order).  Two launches (the engine and a finish kernel), deterministic (no atomics),
+ * enqueue-only, graph-capturable.  workspace: sot_spec_metrics_workspace_bytes() bytes on an 8-byte boundary (0 for arguments outside the domain).
+ * Status: SOT_ERR_UNSUPPORTED_SIZE for a size the engine does not take; SOT_ERR_BAD_SHAPE for n_groups outside 1 .. 4, n_sizes outside
+ * 1 .. 8, a size named twice in the union, a group with no size, with a size that is not in the union or with all three weights <= 0, and
+ * for bad strides; SOT_ERR_NULL_POINTER; SOT_ERR_WORKSPACE -- all decided before anything is enqueued.  batch == 0: SOT_OK, nothing is touched.
+ * (The reference's `mse`, metrics.py:11-13, needs no entry point of its own: sot_spec_distance_forward on the raw audio with mag_weight 1, l2 1.) */
+#define SOT_METRIC_MAX_GROUPS 4
+typedef struct sot_metric_group {
+    int32_t n_sizes;          /* 1 .. 8 */
+    int32_t fft_sizes[8];     /* sizes of the union, in the order the reference's call lists them */
+    float mag_weight, logmag_weight, lsd_weight;
+    int32_t l2;               /* 0: "L1", otherwise "L2" */
+} sot_metric_group;
+size_t sot_spec_metrics_workspace_bytes(int64_t batch, int64_t samples, const int *fft_sizes, int n_sizes, int n_groups);
+int sot_spec_metrics(const float *target, int64_t target_row_stride, const float *value, int64_t value_row_stride, int64_t batch,
+                     int64_t samples, const int *fft_sizes, const float *const *windows, int n_sizes, const sot_metric_group *groups,
+                     int n_groups, float eps, int per_clip, float *out /* [n_groups] or [n_groups, batch] */, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /* ---- Time-invariant FIR filtering of [batch, samples] audio (ABI 15; csrc/sot_fir.hip): the reference's ddsp.fft_convolve for a 2-D
  * impulse response (one frame) with padding="same" (ddsp.py:504-633, crop_and_compensate_delay :695-734) -- what frequency_filter
