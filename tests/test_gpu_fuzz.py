@@ -85,3 +85,24 @@ def test_random_per_row_position_cases_on_every_route(seed):
     assert cases == 250
     assert failures == [], failures[:3]
     assert worst_forward <= 2e-5
+
+
+@pytest.mark.parametrize("seed", [61, 62])
+def test_random_synth_cases_against_float64(seed):
+    """tools/fuzz_synth.py: 60 cases per seed -- random sinusoid count (1 ... 512, every segment length), clip length (1 ... 6000, half of them within
+    9 samples of a segment boundary), batch, entry point (oscillator bank, envelope kernels, one-piece synthesiser with random frames / hop /
+    harmonic), signal kind (random, constant, chirp through Nyquist, all muted, zero amplitudes) and requested gradients -- against the float64
+    model of tests/synth_model.py: every element of audio and gradients within its derived float32 bound (error / bound <= 1), envelopes bit
+    for bit, and at most synth_model.TIE_SHARE of an input's elements on a phase tie."""
+    native()
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import fuzz_synth
+    import synth_model
+    cases, failures, worst_ratio = fuzz_synth.run(budget=120.0, seed0=seed, max_cases=60, verbose=False)
+    stats = fuzz_synth.STATS
+    print(f"seed {seed}: worst error / bound {worst_ratio:.3f}, phase ties {stats['ties']} of {stats['elements']} elements, entries {stats['entries']}")
+    assert cases == 60
+    assert stats["segments"] == {8, 16, 32, 64, 128, 256, 512} and set(stats["entries"]) == {"bank", "envelopes", "synth"}
+    assert failures == [], failures[:3]
+    assert worst_ratio <= 1.0
+    assert fuzz_synth.STATS["worst_tie_share"] <= synth_model.TIE_SHARE

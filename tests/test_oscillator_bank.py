@@ -66,7 +66,7 @@ def test_hip_oscillator_bank_against_torch_autograd(batch, samples, k):
     f1.grad = a1.grad = None
     (got * up).sum().backward()   # the backward reuses the forward's segment phases: a second walk gives the same bits
     assert torch.equal(f1.grad, first[0]) and torch.equal(a1.grad, first[1])
-    # the same composition in float64 on the fp32-rounded phases is not expressible; compare with the CPU composition
+    # against the package's float32 CPU composition (tests/test_synth_geometry_gpu.py compares with the float64 model on the same fp32 phases)
     f2, a2 = f.cpu().clone().requires_grad_(True), a.cpu().clone().requires_grad_(True)
     want = spectra.oscillator_bank(f2, a2, 16000)
     (want * up.cpu()).sum().backward()
