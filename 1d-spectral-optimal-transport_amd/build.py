@@ -10,24 +10,37 @@ import shutil
 import subprocess
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(PKG_DIR, "csrc", "sot_hip.hip")
-STFT_SRC = os.path.join(PKG_DIR, "csrc", "sot_stft.hip")   # the STFT-magnitude producer: its own translation unit
-OSC_SRC = os.path.join(PKG_DIR, "csrc", "sot_osc.hip")     # the oscillator bank
-MSS_SRC = os.path.join(PKG_DIR, "csrc", "sot_mss.hip")     # MSSLoss with its gradient in two launches (round 5)
-FIR_SRC = os.path.join(PKG_DIR, "csrc", "sot_fir.hip")     # time-invariant FIR filter (frequency_filter / the synthesiser's roll-off)
-DEPS = [SRC, STFT_SRC, OSC_SRC, MSS_SRC, FIR_SRC, os.path.join(PKG_DIR, "csrc", "sot_stft_tables.inc"), os.path.join(PKG_DIR, "csrc", "sot_device.hpp"), os.path.join(PKG_DIR, "csrc", "sot_wave_sort.hpp"), os.path.join(PKG_DIR, "csrc", "sot_wave_fft.hpp"), os.path.join(PKG_DIR, "csrc", "sot_forward_full.inc"),
-        os.path.join(os.path.dirname(PKG_DIR), "include", "sot_hip.h")]
+CSRC = os.path.join(PKG_DIR, "csrc")
+# (object name, source): one translation unit each, compiled in parallel and linked into one shared library; the slowest first.
+OBJECTS = (
+    ("full_fwd", "sot_full_fwd.hip"),                    # full-row kernels (sot_forward_full.inc): compile-time row lengths, forward
+    ("full_bwd", "sot_full_bwd.hip"),                    #   ... backward and the merge-free training form
+    ("full_rt_fwd", "sot_full_rt_fwd.hip"),              #   ... run-time row lengths, forward
+    ("full_rt_bwd", "sot_full_rt_bwd.hip"),              #   ... run-time row lengths, backward
+    ("fwd_shared", "sot_fwd_shared.hip"),                # generic kernels (sot_rows.hpp): forward, shared positions, no cutoff
+    ("fwd_shared_cutoff", "sot_fwd_shared_cutoff.hip"),  #   ... with the quantile cutoff
+    ("fwd_rowpos", "sot_fwd_rowpos.hip"),                #   ... per-row positions
+    ("bwd_shared", "sot_bwd_shared.hip"),                # generic backward, shared positions
+    ("bwd_rowpos", "sot_bwd_rowpos.hip"),                #   ... per-row positions
+    ("core", "sot_hip.hip"),                             # small kernels, sorts, launch setup and routing, the C ABI
+    ("csr", "sot_csr.hip"),                              # CSR (ragged) forward
+    ("posgrad", "sot_posgrad.hip"),                      # position gradient, column sum
+    ("quantgrad", "sot_quantgrad.hip"),                  # gradient of the return_quantiles tensors
+    ("stft", "sot_stft.hip"),                            # the STFT-magnitude producer
+    ("osc", "sot_osc.hip"),                              # the oscillator bank
+    ("mss", "sot_mss.hip"),                              # MSSLoss with its gradient in two launches
+    ("fir", "sot_fir.hip"),                              # time-invariant FIR filter (frequency_filter / the synthesiser's roll-off)
+)
+# everything the library is compiled from: whatever csrc/ holds, so that a new header can never be missing from the digest
+DEPS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".inc"))) + [
+    os.path.join(os.path.dirname(PKG_DIR), "include", "sot_hip.h")]
 LIB = os.path.join(PKG_DIR, "libsot_hip.so")
 
 # -ffp-contract=off / -fno-fast-math: the kernels rely on IEEE fp32 division and unfused
 # multiply/add to stay bit-compatible with the reference's CPU arithmetic.
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
-# sot_hip.hip is compiled in parts (-DSOT_PART=<bit>) in parallel and linked into one shared library:
-# compile-time-length forward and backward kernels, forward/shared positions (no cutoff, cutoff), forward/per-row positions,
-# backward/shared, backward/per-row, everything else, CSR forward, position gradients, gradients of the return_quantiles tensors.
-PARTS = (128, 256, 512, 1024, 1, 64, 2, 4, 8, 16, 32, 2048, 4096)   # the longest first (bits 7-10: compile-time-geometry kernels)
-OBJ_DIR = os.path.join(PKG_DIR, "csrc", "obj")
+OBJ_DIR = os.path.join(CSRC, "obj")
 
 
 def hipcc_path() -> str:
@@ -61,31 +74,40 @@ def is_stale() -> bool:
         return f.read().strip() != source_digest()
 
 
-def _compile_part(part, extra_flags, verbose: bool, obj_dir: str = None) -> str:
-    obj_dir = obj_dir or OBJ_DIR
-    if part in ("stft", "osc", "mss", "fir"):
-        obj = os.path.join(obj_dir, f"sot_{part}.o")
-        cmd = [hipcc_path(), *HIPCC_FLAGS, *extra_flags, "-c", "-o", obj, {"stft": STFT_SRC, "osc": OSC_SRC, "mss": MSS_SRC, "fir": FIR_SRC}[part]]
-    else:
-        obj = os.path.join(obj_dir, f"sot_part{part}.o")
-        cmd = [hipcc_path(), *HIPCC_FLAGS, *extra_flags, f"-DSOT_PART={part}", "-c", "-o", obj, SRC]
+def _compile(name: str, extra_flags, verbose: bool, obj_dir: str) -> str:
+    obj = os.path.join(obj_dir, f"sot_{name}.o")
+    cmd = [hipcc_path(), *HIPCC_FLAGS, *extra_flags, "-c", "-o", obj, os.path.join(CSRC, dict(OBJECTS)[name])]
     if verbose:
         print(" ".join(cmd))
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
-        raise RuntimeError(f"hipcc failed on part {part}:\n" + res.stdout + res.stderr)
+        raise RuntimeError(f"hipcc failed on object {name}:\n" + res.stdout + res.stderr)
     return obj
 
 
-def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str = None) -> str:
-    """Compile every kernel instantiation for gfx950 and link libsot_hip.so (parts built in parallel).
+def _compile_all(names, extra_flags, verbose: bool, obj_dir: str) -> dict:
+    from concurrent.futures import ThreadPoolExecutor
+    os.makedirs(obj_dir, exist_ok=True)
+    workers = max(1, min(13, (os.cpu_count() or 2)))   # 13: the row-kernel objects, which take longest
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        return dict(zip(names, pool.map(lambda name: _compile(name, tuple(extra_flags), verbose, obj_dir), names)))
+
+
+def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str = None, only=None) -> str:
+    """Compile every kernel instantiation for gfx950 and link libsot_hip.so (objects built in parallel).
 
     One builder at a time per tree (an exclusive lock on a file next to the library: several ranks that find the library
     stale at once would otherwise compile into the same object files).  The digest is removed before anything is
     overwritten and only written back for a flag-free build into the product path, so a diagnostic build (extra_flags)
-    that lands on libsot_hip.so is never mistaken for the product library by is_stale()."""
+    that lands on libsot_hip.so is never mistaken for the product library by is_stale().
+
+    only=(names of OBJECTS...), with extra_flags and out: a variant library in which just the named objects carry the extra
+    flags; the rest are the product objects (the product library is built first when it is stale; its digest is not touched)."""
     import fcntl
-    from concurrent.futures import ThreadPoolExecutor
+    if only is not None:
+        if out is None or not set(only) <= set(dict(OBJECTS)):
+            raise ValueError("only= takes names of build.OBJECTS and needs out")
+        build(verbose=verbose, force=not all(os.path.exists(os.path.join(OBJ_DIR, f"sot_{name}.o")) for name, _ in OBJECTS))
     lib = out or LIB
     if not force and out is None and not is_stale():
         return lib
@@ -98,11 +120,10 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
             os.remove(DIGEST)
         # diagnostic variants (out / extra_flags) get their own object directory: they never mix with the product objects
         obj_dir = OBJ_DIR if (out is None and not extra_flags) else os.path.join(OBJ_DIR, "variant_%d" % os.getpid())
-        os.makedirs(obj_dir, exist_ok=True)
-        workers = max(1, min(len(PARTS), (os.cpu_count() or 2)))
-        with ThreadPoolExecutor(max_workers=workers) as pool:
-            objs = list(pool.map(lambda part: _compile_part(part, tuple(extra_flags), verbose, obj_dir), (*PARTS, "stft", "osc", "mss", "fir")))
-        cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib + ".tmp", *objs]
+        names = [name for name, _ in OBJECTS]
+        objs = {name: os.path.join(OBJ_DIR, f"sot_{name}.o") for name in names} if only is not None else {}
+        objs.update(_compile_all([n for n in names if only is None or n in only], extra_flags, verbose, obj_dir))
+        cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib + ".tmp", *(objs[n] for n in names)]
         if verbose:
             print(" ".join(cmd))
         res = subprocess.run(cmd, capture_output=True, text=True)
@@ -118,7 +139,7 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
 
 
 # ---- the C++ host path of the module (csrc/sot_torch_glue.cpp): a torch extension WITHOUT device code, built in-tree -----------
-GLUE_SRC = os.path.join(PKG_DIR, "csrc", "sot_torch_glue.cpp")
+GLUE_SRC = os.path.join(CSRC, "sot_torch_glue.cpp")
 GLUE_LIB = os.path.join(PKG_DIR, "_sot_glue.so")
 GLUE_DIGEST = GLUE_LIB + ".digest"
 

@@ -1,4 +1,7 @@
-// sot_forward_full.inc -- included by sot_hip.hip (inside namespace sot) when build part bit 7 is selected.
+// sot_forward_full.inc -- kernel and launch templates of the full-row kernels (compile-time geometries), namespace sot.  Included by
+// the four objects that instantiate them: sot_full_fwd.hip, sot_full_bwd.hip (compile-time row lengths), sot_full_rt_fwd.hip,
+// sot_full_rt_bwd.hip (run-time row lengths).  The non-template dispatch functions live there: dispatch_forward_full and
+// dispatch_area_full in sot_full_fwd.hip, dispatch_backward_full and dispatch_area_train in sot_full_bwd.hip.
 //
 // Full-row forward kernel: the row pipeline of sot_forward_kernel for row lengths known at compile time: rows that fill
 // their geometry exactly (n == m == G*CPT = 512, 2048 or 8192; 16-B aligned rows) and the paper's 257 / 513 / 1025 bins
@@ -13,6 +16,10 @@
 // the row regions with the same internal offsets, so that "position of the element at LDS offset o of row r" is
 // o + (ROWS - r) * rowf: a compile-time immediate per row group (512-bin rows: four rows per 256-thread workgroup).
 // Reference semantics: losses.py:172-196, :271-313, :214-220; utils.py:135-142.
+#pragma once
+#include "sot_launch.hpp"
+
+namespace sot {
 
 // Diagnostic build only (-DSOT_STAMPS): thread 0 of one workgroup adds up, per phase of its rows, the shader clocks between
 // consecutive checkpoints (sacc[i] += now - sacc[15]; sacc[15] = now) and stores the sums at the end; no output depends on them.
@@ -846,7 +853,6 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? kRt512MinWaves : (
     if (a.mt.counters != nullptr) batch_mean_tail<ROWS * G>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
 }
 
-
 // ---------------------------------------------------------------------------------------------
 // Merge-free forward for p = 1 when both measures live on ONE sorted grid (SOT_FLAG_SAME_GRID; every reference call site:
 // y_pos = x_pos.clone() in trainer.py:191, the fixed_x buffer of metrics.py:148), no quantile cutoff.
@@ -1188,7 +1194,6 @@ __global__ __launch_bounds__(ROWS * 32) void sot_forward_half_kernel(const FwdAr
     if (a.mt.counters != nullptr) batch_mean_tail<ROWS * 32>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
 }
 
-#if SOT_FULL_FWD || SOT_FULL_RT_FWD
 template <int G, int CPT, int ROWS, bool SQ, int NX>
 static hipError_t launch_area_full(const FwdArgs& a, hipStream_t s)
 {
@@ -1211,7 +1216,6 @@ static hipError_t dispatch_area_full_g(const FwdArgs& a, hipStream_t s)
     return (a.flags & SOT_FLAG_SQUARE) ? launch_area_full<G, CPT, ROWS, true, NX>(a, s) : launch_area_full<G, CPT, ROWS, false, NX>(a, s);
 }
 
-
 template <int CPT, int ROWS, int N>
 static hipError_t dispatch_area_half(const FwdArgs& a, hipStream_t s)
 {
@@ -1230,31 +1234,6 @@ static hipError_t dispatch_area_half(const FwdArgs& a, hipStream_t s)
     }
     return hipGetLastError();
 }
-#endif
-#if SOT_FULL_FWD
-// Preconditions: those of dispatch_forward_full, plus p == 1, no quantile cutoff, SOT_FLAG_SAME_GRID.
-hipError_t dispatch_area_full(const FwdArgs& a, hipStream_t s)
-{
-    switch (a.n) {
-        case 512: return dispatch_area_full_g<64, 8, 4>(a, s);
-        case 1024: return dispatch_area_full_g<128, 8, 2>(a, s);
-        case 2048: return dispatch_area_full_g<256, 8, 1>(a, s);
-        case 4096: return dispatch_area_full_g<512, 8, 1>(a, s);
-        case 8192: return dispatch_area_full_g<1024, 8, 1>(a, s);
-        case 129:   // two rows per wave: 65536 rows 25.3 -> 20.6 us, 4096 rows 7.9 -> 7.7 us
-            return dispatch_area_half<5, 8, 129>(a, s);
-        case 2049: return dispatch_area_full_g<256, 9, 1, 2049>(a, s);
-        case 257:   // (two rows per wave: 65536 rows 33.0 -> 32.0 us, 16384 rows 10.2 -> 10.8 us: this kernel is at the HBM limit for 257-bin rows already)
-            return dispatch_area_full_g<64, 5, 4, 257>(a, s);
-        case 513: return dispatch_area_full_g<64, 9, 4, 513>(a, s);
-        case 1025:   // one wave per row (17 elements per thread, no workgroup barrier): 1024 / 4096 rows as before (7.4 / 10.7 us), 8192 rows 18.7 -> 16.9 us,
-                     // 16384 rows 31.3 -> 29.2 us against <128, 9, 2> (interleaved A/B)
-            return dispatch_area_full_g<64, 17, 4, 1025>(a, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
-#endif  // SOT_FULL_FWD
 
 // ---------------------------------------------------------------------------------------------
 // Full-row backward kernel: sot_backward_kernel (closed form of the autograd graph, see there) for the same rows the
@@ -1644,7 +1623,6 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
     }
 }
 
-#if SOT_FULL_BWD
 // ---------------------------------------------------------------------------------------------
 // Merge-free TRAINING FORM for p = 1 on one grid (round 4): row loss and d(grad_scale * sum_r row_loss) / dy out of
 // sot_area_full_kernel's pipeline.  With loss = sum_{i < n-1} |U_i - V_i| (xs_{i+1} - xs_i) (see sot_area_full_kernel) and
@@ -1814,26 +1792,6 @@ static hipError_t dispatch_area_train_g(const BwdArgs& b, hipStream_t s)
     return (b.f.flags & SOT_FLAG_SQUARE) ? launch_area_train<G, CPT, ROWS, true, NX>(b, s) : launch_area_train<G, CPT, ROWS, false, NX>(b, s);
 }
 
-// Preconditions: those of dispatch_backward_full with gx == nullptr, plus p == 1, no quantile cutoff, SOT_FLAG_SAME_GRID.
-hipError_t dispatch_area_train(const BwdArgs& b, hipStream_t s)
-{
-    switch (b.f.n) {
-        case 512: return dispatch_area_train_g<64, 8, 4>(b, s);
-        case 1024: return dispatch_area_train_g<128, 8, 2>(b, s);
-        case 2048: return dispatch_area_train_g<256, 8, 1>(b, s);
-        case 4096: return dispatch_area_train_g<512, 8, 1>(b, s);
-        case 129: return dispatch_area_train_g<64, 3, 4, 129>(b, s);
-        case 257: return dispatch_area_train_g<64, 5, 4, 257>(b, s);
-        case 513: return dispatch_area_train_g<64, 9, 4, 513>(b, s);
-        case 1025: return dispatch_area_train_g<128, 9, 2, 1025>(b, s);   // (one wave per row, 64 x 17 as the forward: 208 VGPRs, 96 us at 16384 rows)
-        case 2049: return dispatch_area_train_g<256, 9, 1, 2049>(b, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-bool area_train_supports(int n) { return n == 512 || n == 1024 || n == 2048 || n == 4096 || n == 129 || n == 257 || n == 513 || n == 1025 || n == 2049; }
-#endif  // SOT_FULL_BWD (merge-free training form)
-
-#if SOT_FULL_FWD || SOT_FULL_RT_FWD
 template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool RP = false>
 static hipError_t launch_forward_full(const FwdArgs& a, hipStream_t s)
 {
@@ -1841,7 +1799,7 @@ static hipError_t launch_forward_full(const FwdArgs& a, hipStream_t s)
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
     const size_t lds = sizeof(float) * (size_t)L.total;
     constexpr int block = ROWS * G;
-    static GridCache cache;  // per instantiation, per device (sot_hip.hip: cached_resident_grid)
+    static GridCache cache;  // per instantiation, per device (sot_launch.hpp: cached_resident_grid)
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
     const int64_t want = (a.B + ROWS - 1) / ROWS;
     const int grid = persistent_grid(want, grid_cap);
@@ -1875,9 +1833,6 @@ static hipError_t dispatch_forward_full_g(int pm, const FwdArgs& a, hipStream_t 
     }
 }
 
-#endif  // SOT_FULL_FWD || SOT_FULL_RT_FWD
-
-#if SOT_FULL_FWD
 // Per-row positions with handed-over permutations on the compile-time geometries of 2048- / 1024- / 512-point rows, ONE row per workgroup (round 6).
 // Preconditions (run_forward): n == m in {512, 1024, 2048}, rows and permutation rows 16-byte aligned, a.perm_in complete, SOT_FLAG_REQUIRE_SORT.
 template <int G>
@@ -1901,80 +1856,7 @@ static hipError_t dispatch_forward_full_rowpos_g(int pm, const FwdArgs& a, hipSt
         default: return launch_forward_full<G, 8, 1, 0, true, true, 0, true>(a, s);
     }
 }
-hipError_t dispatch_forward_full_rowpos(int pm, const FwdArgs& a, hipStream_t s)
-{
-    switch (a.n) {
-        case 2048: return dispatch_forward_full_rowpos_g<256>(pm, a, s);
-        case 1024: return dispatch_forward_full_rowpos_g<128>(pm, a, s);
-        case 512: return dispatch_forward_full_rowpos_g<64>(pm, a, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-#endif
 
-#if SOT_FULL_RT_FWD
-int full_rt_capacity(int n);
-hipError_t dispatch_forward_full_rt(int pm, const FwdArgs& a, hipStream_t s)
-{
-    switch (full_rt_capacity(a.n)) {
-        case 256: return dispatch_forward_full_g<64, 4, 4, -1>(pm, a, s);
-        case 512: return dispatch_forward_full_g<64, 8, 4, -1>(pm, a, s);
-        case 1024:   // large batches: one wave per row (16384 x 1000 paper mode 54.9 -> 50.6 us, 8192 rows 30.4 -> 29.9, 4096 rows 17.5 -> 19.2)
-            if (a.B >= kRt1024OneWaveRows) return dispatch_forward_full_g<64, 16, 4, -1>(pm, a, s);
-            return dispatch_forward_full_g<128, 8, 2, -1>(pm, a, s);
-        case 1536: return dispatch_forward_full_g<192, 8, 1, -1>(pm, a, s);
-        case 2048:   // (two waves per row, 16 elements per thread: 53.6 vs 53.9 us at 8192 x 2000 -- nothing; one row per workgroup 64.3 us)
-            return dispatch_forward_full_g<256, 8, 1, -1>(pm, a, s);
-        case 3072: return dispatch_forward_full_g<384, 8, 1, -1>(pm, a, s);
-        case 4096: return dispatch_forward_full_g<512, 8, 1, -1>(pm, a, s);
-        case 8192: return dispatch_forward_full_g<1024, 8, 1, -1>(pm, a, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
-hipError_t dispatch_area_full_rt(const FwdArgs& a, hipStream_t s)
-{
-    switch (full_rt_capacity(a.n)) {
-        case 256: return dispatch_area_full_g<64, 4, 4, -1>(a, s);
-        case 512: return dispatch_area_full_g<64, 8, 4, -1>(a, s);
-        // 1024-point geometry: one wave per row (16 elements per thread) -- 16384 x 1000 48.2 -> 40.4 us, 8192 rows 27.6 -> 23.3, 4096 rows
-        // 17.0 -> 15.3, 2048 / 1024 rows as before; the 2048-point geometry with two waves per row instead of four: 46.6 -> 52.8 us, stays
-        case 1024: return dispatch_area_full_g<64, 16, 4, -1>(a, s);
-        case 1536: return dispatch_area_full_g<192, 8, 1, -1>(a, s);
-        case 2048: return dispatch_area_full_g<256, 8, 1, -1>(a, s);   // (two waves per row, one row per 128-thread workgroup: 53.6 us)
-        case 3072: return dispatch_area_full_g<384, 8, 1, -1>(a, s);
-        case 4096: return dispatch_area_full_g<512, 8, 1, -1>(a, s);
-        case 8192: return dispatch_area_full_g<1024, 8, 1, -1>(a, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-#endif  // SOT_FULL_RT_FWD
-
-#if SOT_FULL_FWD
-// Run-time row lengths (NX = -1): any n == m <= 8192 on shared positions runs the compile-time GEOMETRY of the next capacity
-// (256 / 512 / 1024 / 2048 / 4096 / 8192 points; the backward up to 4096).  Replaces the generic kernels for such rows:
-// 8192 x 2000 forward 70 -> ~50 us, training form 192 -> ~90 us (DESIGN section 5).
-int full_rt_capacity(int n)
-{
-    if (n <= 128) return 0;    // tiny rows: the generic (64, 8) kernel wastes less
-    for (int cap = 256; cap <= 8192; cap <<= 1) {
-        // 1536 = 192 x 8, 3072 = 384 x 8: rows just above a power of two do not pay for twice their length
-        if (cap >= 2048 && cap <= 4096 && n <= cap - cap / 4) return cap - cap / 4;
-        if (n <= cap) return cap;
-    }
-    return 0;
-}
-
-// Row lengths with a compile-time kernel: 512 / 1024 / 2048 / 4096 / 8192 bins (16-B aligned rows required) and the
-// one-sided spectra of n_fft 256 ... 4096: 129 / 257 / 513 / 1025 / 2049 bins (the paper uses 257 and 1025; any alignment).
-bool forward_full_supports(int n, bool aligned16)
-{
-    return ((n == 512 || n == 1024 || n == 2048 || n == 4096 || n == 8192) && aligned16) || n == 129 || n == 257 || n == 513 ||
-           n == 1025 || n == 2049;
-}
-
-// The caller (run_forward) guarantees: shared positions, n == m with forward_full_supports(n, ...), p in {1, 2}, not
-// pre-normalised.  LDS size, block size and grid are this kernel's own (shared-position layout).
 template <int CPT, int ROWS, int PM, bool LIM, bool SQ, int N>
 static hipError_t launch_forward_half(const FwdArgs& a, hipStream_t s)
 {
@@ -2010,43 +1892,6 @@ static hipError_t dispatch_forward_half(int pm, const FwdArgs& a, hipStream_t s)
     }
 }
 
-hipError_t dispatch_forward_full(const LaunchCfg&, int pm, const FwdArgs& a, size_t, int64_t, int, hipStream_t s)
-{
-    switch (a.n) {
-        case 512: return dispatch_forward_full_g<64, 8, 4>(pm, a, s);
-        case 1024: return dispatch_forward_full_g<128, 8, 2>(pm, a, s);
-        case 2048: return dispatch_forward_full_g<256, 8, 1>(pm, a, s);
-        case 4096: return dispatch_forward_full_g<512, 8, 1>(pm, a, s);
-        case 8192: return dispatch_forward_full_g<1024, 8, 1>(pm, a, s);
-        case 129:   // large batches: two rows per wave (sot_forward_half_kernel).  Paper mode, interleaved A/B: 8192 rows 7.5 -> 6.9 us, 16384 rows 11.7 -> 10.4,
-                    // 32768 rows 19.8 -> 16.0, 65536 rows 35.0 -> 28.0 us
-            if (a.B >= 8192) return dispatch_forward_half<5, 8, 129>(pm, a, s);
-            return dispatch_forward_full_g<64, 3, 4, 129>(pm, a, s);
-        case 2049: return dispatch_forward_full_g<256, 9, 1, 2049>(pm, a, s);
-        case 257:   // the same from ~40 000 rows: 16384 rows 15.5 -> 16.8 us, 32768 rows 25.6 -> 26.4, 49152 rows 40.4 -> 37.4, 65536 rows 53.0 -> 47.8 us
-                    // (each row region carries its own copy of the positions -- the walk addresses a level's position at a constant offset -- so
-                    // LDS holds 32 rows = 16 waves per CU: fewer, longer-running waves than the one-wave kernel, which only pays once the launch is long)
-            if (a.B >= 40960) return dispatch_forward_half<9, 8, 257>(pm, a, s);
-            return dispatch_forward_full_g<64, 5, 4, 257>(pm, a, s);
-        case 513: return dispatch_forward_full_g<64, 9, 4, 513>(pm, a, s);
-        case 1025:
-            // Large batches: ONE wave per row (17 elements per thread, four rows per workgroup, no workgroup barrier anywhere in the row).
-            // Interleaved A/B against two waves per row, paper mode: 1024 rows 7.5 -> 8.4 us, 4096 rows 15.5 -> 15.5, 6144 rows 20.3 ->
-            // 19.3, 8192 rows 25.6 -> 23.3, 12288 rows 35.3 -> 31.6, 16384 rows 45.1 -> 42.2 us.  (Its thread-local sums group the row
-            // differently: row losses agree with the two-wave kernels' to ~1e-7, not bit for bit.  The training kernel in this
-            // geometry needs 17-element gradient arrays in registers and is slower: 85 -> 107 us at 16384 rows.)
-            if (a.B >= kFwd1025OneWaveRows) return dispatch_forward_full_g<64, 17, 4, 1025>(pm, a, s);
-            return dispatch_forward_full_g<128, 9, 2, 1025>(pm, a, s);  // 256 threads per row: 64.6 instead of 54.4 us at 16384 rows (round 1)
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
-// Same preconditions as dispatch_forward_full, without 8192-bin rows (8192 + 8192 bins with gradient arrays exceed the LDS);
-// for 512 / 2048 bins the gradient buffers must be 16-B aligned as well.
-bool backward_full_supports(int n, bool aligned16) { return n != 8192 && forward_full_supports(n, aligned16); }
-#endif  // SOT_FULL_FWD
-
-#if SOT_FULL_BWD || SOT_FULL_RT_BWD
 template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool WANT_X, bool SLIM = false, int MINB = 1, bool RP = false>
 static hipError_t launch_backward_full_x(const BwdArgs& b, hipStream_t s)
 {
@@ -2054,7 +1899,7 @@ static hipError_t launch_backward_full_x(const BwdArgs& b, hipStream_t s)
     constexpr FullLayout L = full_layout<G, CPT, ROWS, SLIM ? 2 : 1, NX>();
     const size_t lds = sizeof(float) * (size_t)L.total;
     constexpr int block = ROWS * G;
-    static GridCache cache;  // per instantiation, per device (sot_hip.hip: cached_resident_grid)
+    static GridCache cache;  // per instantiation, per device (sot_launch.hpp: cached_resident_grid)
     const int grid_cap = cached_resident_grid(cache, kern, block, lds);
     const int64_t want = (b.f.B + ROWS - 1) / ROWS;
     const int grid = persistent_grid(want, grid_cap);
@@ -2121,66 +1966,6 @@ static hipError_t dispatch_backward_full_y(int pm, const BwdArgs& b, hipStream_t
     }
 }
 
-#endif  // SOT_FULL_BWD || SOT_FULL_RT_BWD
-
-#if SOT_FULL_RT_BWD
-int full_rt_capacity(int n);
-// y-only (training) kernels in the layout without U gradient slots, as the compile-time kernels of 1024 / 2048 points, capped at 128
-// VGPRs (MINB 4) so that the smaller region does buy another resident workgroup.  Interleaved A/B against the full layout (bit-identical
-// results): 1024-point geometry 16384 x 1000 paper mode 106.1 -> 96.6 us -- adopted; 2048-point geometry 8192 x 2000 paper mode
-// 109.1 -> 111.6 us -- the spills cost what the fourth row buys; stays in the full layout.
-// run-time row lengths (see full_rt_capacity): both-gradient and y-only (training form: also the row losses) kernels
-hipError_t dispatch_backward_full_rt(int pm, const BwdArgs& b, hipStream_t s)
-{
-    switch (full_rt_capacity(b.f.n)) {
-        case 256: return dispatch_backward_full_g<64, 4, 4, -1>(pm, b, s);
-        case 512: return dispatch_backward_full_g<64, 8, 4, -1>(pm, b, s);
-        case 1024:
-            if (b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, -1, true, 4>(pm, b, s);
-            return dispatch_backward_full_g<128, 8, 2, -1, 1>(pm, b, s);
-        case 1536: return dispatch_backward_full_g<192, 8, 1, -1>(pm, b, s);
-        case 2048: return dispatch_backward_full_g<256, 8, 1, -1>(pm, b, s);
-        case 3072: return dispatch_backward_full_g<384, 8, 1, -1>(pm, b, s);
-        case 4096: return dispatch_backward_full_g<512, 8, 1, -1>(pm, b, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-#endif  // SOT_FULL_RT_BWD
-
-#if SOT_FULL_BWD
-// Rows per workgroup of the y-only (training) kernel for 2048-bin rows.  Without gradient slots for U two rows and the shared
-// position copy take 68.7 KB: two workgroups = four rows per CU instead of three (one row with U slots + positions: 50.9 KB).
-// Measured at 8192 x 2048, paper mode: 79.7 instead of 81.5 us.
-hipError_t dispatch_backward_full(const LaunchCfg&, int pm, const BwdArgs& b, hipStream_t s)
-{
-    switch (b.f.n) {
-        case 512: return dispatch_backward_full_g<64, 8, 4>(pm, b, s);   // (the slim layout adds a fourth workgroup per CU here too: 64.5 vs 65.0 us, nothing)
-        case 1024:   // y-only: 34.8 instead of 43.3 KB per two rows = eight rows per CU instead of six: 16384 rows 78.8 -> 73.4 us, 4096 rows 27.3 -> 26.0 us
-            if (b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, 0, true, 1>(pm, b, s);
-            return dispatch_backward_full_g<128, 8, 2, 0, 1>(pm, b, s);
-        case 2048:
-            if (b.gx == nullptr) return dispatch_backward_full_y<256, 8, 2>(pm, b, s);
-            return dispatch_backward_full_g<256, 8, 1, 0, 1>(pm, b, s);
-        case 4096: return dispatch_backward_full_g<512, 8, 1>(pm, b, s);
-        case 129: return dispatch_backward_full_g<64, 3, 4, 129>(pm, b, s);
-        case 2049:   // y-only: 47.7 instead of 57 KB per row = three rows per CU instead of two: 8192 rows 119.2 -> 95.5 us
-            if (b.gx == nullptr) return dispatch_backward_full_y<256, 9, 1, 2049, true, 1>(pm, b, s);
-            return dispatch_backward_full_g<256, 9, 1, 2049, 1>(pm, b, s);
-        case 257:
-            return dispatch_backward_full_g<64, 5, 4, 257>(pm, b, s);
-        case 513:
-            // y-only: the layout without U gradient slots (35.5 KB per four rows): 8192 rows 26.6 -> 25.0 us, 32768 rows 75.8 -> 74.5 us
-            if (b.gx == nullptr) return dispatch_backward_full_y<64, 9, 4, 513, true, 4>(pm, b, s);
-            return dispatch_backward_full_g<64, 9, 4, 513, 1>(pm, b, s);
-        case 1025:
-            // y-only (training) kernel: the layout without U gradient slots (39 KB per two rows) compiled for four workgroups per CU
-            // (128 VGPRs, 9 dwords spilled) holds eight rows per CU instead of six: 4096 rows 30.8 -> 29.1 us, 16384 rows 88.9 -> 85.6 us
-            if (b.gx == nullptr) return dispatch_backward_full_y<128, 9, 2, 1025, true, 4>(pm, b, s);
-            return dispatch_backward_full_g<128, 9, 2, 1025, 1>(pm, b, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
 // Per-row positions with handed-over permutations on the 2048-point geometry (round 6; see sot_forward_full_kernel: RP).  One row per workgroup;
 // gradient w.r.t. y alone: the layout without U gradient slots, and the row loss on the walk (the training form).  Gradients leave through the permutation
 // (scattered 4-byte stores inside the row's 8 KB).
@@ -2211,15 +1996,5 @@ static hipError_t dispatch_backward_full_rowpos_g(int pm, const BwdArgs& b, hipS
         default: return launch_backward_full_rowpos<G, 0, true, true>(b, s);
     }
 }
-hipError_t dispatch_backward_full_rowpos(int pm, const BwdArgs& b, hipStream_t s)
-{
-    switch (b.f.n) {
-        case 2048: return dispatch_backward_full_rowpos_g<256>(pm, b, s);
-        case 512: return dispatch_backward_full_rowpos_g<64>(pm, b, s);
-        // (1024-point rows stay on the generic kernel: its 128 x 12 partition of the fp64 sums rounds a handful of near-zero gradient entries another
-        // way than 128 x 8 would -- <= 9e-8 of the row's scale on clustered / degenerate rows, tools/r6/fuzz_rowpos.py -- and every per-row route giving
-        // the same bits is worth more than that shape's backward time; 2048 and 512 share the generic kernel's partition)
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-#endif  // SOT_FULL_BWD
+
+}  // namespace sot

@@ -1,0 +1,222 @@
+// sot_launch.hpp -- host side shared by the row-kernel objects: launch configuration (pick_cfg), resident-grid caches, argument
+// validation, workspace layout, kernel-attached timing, and the declarations of what one object calls in another.
+#pragma once
+#include "sot_rows.hpp"
+
+namespace sot {
+
+// ---------------------------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------------------------
+constexpr size_t kLdsLimit = 160 * 1024;
+
+// Allow a kernel to use up to the CU's full 160 KiB of dynamic LDS; leaves no sticky error behind.
+static inline void allow_full_lds(const void* kernel)
+{
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit) != hipSuccess)
+        (void)hipGetLastError();
+}
+
+// Launch state is kept PER DEVICE and behind a mutex: a process may use several GPUs (the binding switches devices per
+// call), and calls arrive from several host threads (autograd runs backward on its own thread; ctypes drops the GIL).
+constexpr int kMaxDevices = 64;
+static inline int current_device()
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    return dev;
+}
+
+static inline int device_cu_count()
+{
+    static std::mutex mu;
+    static int cus[kMaxDevices] = {};
+    const int dev = current_device();
+    const bool cacheable = dev >= 0 && dev < kMaxDevices;
+    std::lock_guard<std::mutex> lock(mu);
+    if (cacheable && cus[dev] > 0) return cus[dev];
+    hipDeviceProp_t prop;
+    int n = 256;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
+    else (void)hipGetLastError();
+    if (cacheable) cus[dev] = n;
+    return n;
+}
+
+struct LaunchCfg { int G, CPT; };
+
+// Row-group geometries: (threads per row, contiguous elements per thread).  G*CPT >= max(n, m).
+// (128,12) serves the paper's row lengths just above 1024 (n_fft 2048 -> 1025 bins): two rows per workgroup.
+static inline bool pick_cfg(int n, int m, bool rowpos, bool with_grad, LaunchCfg* cfg, size_t* lds_bytes, int* block, int* rpw)
+{
+    const int N = n > m ? n : m;
+    static const LaunchCfg table[] = {{64, 8}, {128, 12}, {256, 8}, {1024, 8}, {1024, 16}};
+    for (int ci = 0; ci < 5; ++ci) {
+        const LaunchCfg& c = table[ci];
+        if ((int64_t)c.G * c.CPT < N) continue;
+        const int blk = c.G < 256 ? 256 : c.G;
+        const int r = blk / c.G;
+        const RowLayout L = make_layout(n, m, c.G, rowpos, with_grad);
+        const size_t bytes = (size_t)r * L.row_floats * sizeof(float);
+        if (bytes > kLdsLimit) continue;
+        *cfg = c; *lds_bytes = bytes; *block = blk; *rpw = r;
+        return true;
+    }
+    return false;
+}
+
+// Persistent grid: exactly as many workgroups as are co-resident (registers, LDS and wave slots all
+// taken into account by the occupancy query), never more than there are row groups.
+template <typename Kernel>
+static inline int resident_grid(Kernel kern, int block, size_t lds, int64_t want)
+{
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, lds) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    const int64_t cap = (int64_t)device_cu_count() * per_cu;
+    return (int)(want < cap ? want : cap);
+}
+
+// resident_grid() of one kernel instantiation, cached per device (and per LDS size: the generic kernels' LDS request
+// depends on n, m); the first use on a device also opts the kernel in to the CU's full LDS THERE (hipFuncSetAttribute
+// applies to the current device only).  One cache per call site: `Tag` is the kernel's own function-pointer type.
+struct GridCache {
+    std::mutex mu;
+    struct Entry { size_t lds; int grid; bool attr; } e[kMaxDevices] = {};
+};
+
+// Grid of a persistent kernel whose workgroups stride over `want` row groups, at most `cap` of them resident (some run one
+// round more: splitting the rows evenly over fewer workgroups was measured 5 % slower for the training form).
+static inline int persistent_grid(int64_t want, int cap)
+{
+    return want <= cap ? (int)want : cap;
+}
+
+template <typename Kernel>
+static inline int cached_resident_grid(GridCache& gc, Kernel kern, int block, size_t lds)
+{
+    const int dev = current_device();
+    if (dev < 0 || dev >= kMaxDevices) {
+        allow_full_lds(reinterpret_cast<const void*>(kern));
+        return resident_grid(kern, block, lds, INT32_MAX);
+    }
+    std::lock_guard<std::mutex> lock(gc.mu);
+    GridCache::Entry& e = gc.e[dev];
+    if (!e.attr) { allow_full_lds(reinterpret_cast<const void*>(kern)); e.attr = true; }
+    if (e.grid == 0 || e.lds != lds) { e.grid = resident_grid(kern, block, lds, INT32_MAX); e.lds = lds; }
+    return e.grid;
+}
+
+// once per device: opt `kernel` in to the full LDS (kernels launched with a fixed grid)
+static inline void allow_full_lds_once(GridCache& gc, const void* kernel)
+{
+    const int dev = current_device();
+    if (dev < 0 || dev >= kMaxDevices) { allow_full_lds(kernel); return; }
+    std::lock_guard<std::mutex> lock(gc.mu);
+    if (!gc.e[dev].attr) { allow_full_lds(kernel); gc.e[dev].attr = true; }
+}
+
+static inline int validate(const sot_problem* pr)
+{
+    if (pr == nullptr) return SOT_ERR_NULL_POINTER;
+    if (!(pr->p >= 1.0f)) return SOT_ERR_INVALID_P;
+    if (pr->B < 0 || pr->n < 1 || pr->m < 1) return SOT_ERR_BAD_SHAPE;
+    if (pr->x_row_stride < pr->n || pr->y_row_stride < pr->m) return SOT_ERR_BAD_SHAPE;
+    if (pr->xpos_row_stride != 0 && pr->xpos_row_stride < pr->n) return SOT_ERR_BAD_SHAPE;
+    if (pr->ypos_row_stride != 0 && pr->ypos_row_stride < pr->m) return SOT_ERR_BAD_SHAPE;
+    if ((pr->xpos_row_stride == 0) != (pr->ypos_row_stride == 0)) return SOT_ERR_BAD_SHAPE;
+    if (pr->B > 0 && (!pr->x || !pr->y || !pr->xpos || !pr->ypos)) return SOT_ERR_NULL_POINTER;
+    return SOT_OK;
+}
+
+static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct WsLayout { size_t sx, sy, px, py, ident, total; };
+// the permutation image of a per-row-position call (setup_launch: the pre-sort kernel's output when the caller passes no row_perm_out)
+static inline size_t rowpos_perm_bytes(int64_t B, int n, int m) { return align_up((size_t)B * ((size_t)n + (size_t)m) * sizeof(uint16_t), 256); }
+
+static inline WsLayout ws_layout(int n, int m)
+{
+    WsLayout w;
+    size_t o = 0;
+    w.sx = o; o = align_up(o + sizeof(float) * (size_t)n, 256);
+    w.sy = o; o = align_up(o + sizeof(float) * (size_t)m, 256);
+    w.px = o; o = align_up(o + sizeof(int) * (size_t)n, 256);
+    w.py = o; o = align_up(o + sizeof(int) * (size_t)m, 256);
+    w.ident = o; o = align_up(o + 2 * sizeof(int), 256);
+    w.total = o;
+    return w;
+}
+
+// ---- kernel-attached timing (sot_profile_next_launch, include/sot_hip.h): when armed by the calling thread, the next launch of
+// a full-row kernel goes through hipExtLaunchKernelGGL with a start / stop event pair of the library's ring, i.e. the events
+// bracket the dispatch itself (what rocprofv3's kernel trace measures) instead of stream time around it.
+bool profile_take(hipEvent_t* start, hipEvent_t* stop);
+
+template <typename Kernel, typename Args>
+static inline void launch_maybe_profiled(Kernel kern, int grid, int block, size_t lds, hipStream_t s, const Args& a)
+{
+    hipEvent_t e0, e1;
+    if (profile_take(&e0, &e1)) hipExtLaunchKernelGGL(kern, dim3(grid), dim3(block), (uint32_t)lds, s, e0, e1, 0, a);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, a);
+}
+
+// ---- cross-object host interface (the objects are linked into one shared library; each function names its defining file) ----
+struct Launch {
+    FwdArgs a;
+    LaunchCfg cfg;
+    size_t lds;
+    int block;
+    int64_t want;  // row groups' worth of workgroups
+    bool rowpos, vec;
+    int pm;        // cost specialisation: 1 -> p == 1, 2 -> p == 2, 0 -> general
+    hipStream_t s;
+};
+
+// sot_fwd_shared.hip (ROWPOS = false), sot_fwd_rowpos.hip (true); sot_bwd_shared.hip, sot_bwd_rowpos.hip
+template <bool ROWPOS>
+hipError_t dispatch_forward(const LaunchCfg& c, bool quant, int pm, bool vec, const FwdArgs& a, size_t lds, int64_t want, int block,
+                            hipStream_t s);
+template <bool ROWPOS>
+hipError_t dispatch_backward(const LaunchCfg& c, int pm, bool vec, const BwdArgs& b, size_t lds, int64_t want, int block,
+                             hipStream_t s);
+// sot_full_fwd.hip
+hipError_t dispatch_forward_full(const LaunchCfg& c, int pm, const FwdArgs& a, size_t lds, int64_t want, int block, hipStream_t s);
+hipError_t dispatch_forward_full_rowpos(int pm, const FwdArgs& a, hipStream_t s);   // per-row positions through handed-over permutations, 2048-point rows (round 6)
+hipError_t dispatch_area_full(const FwdArgs& a, hipStream_t s);
+bool forward_full_supports(int n, bool aligned16);
+bool backward_full_supports(int n, bool aligned16);
+int full_rt_capacity(int n);   // capacity of the compile-time geometry that takes a run-time row length n (0: none)
+// sot_full_bwd.hip
+hipError_t dispatch_backward_full(const LaunchCfg& c, int pm, const BwdArgs& b, hipStream_t s);
+hipError_t dispatch_backward_full_rowpos(int pm, const BwdArgs& b, hipStream_t s);   // per-row positions through handed-over permutations, 2048-point rows (round 6)
+hipError_t dispatch_area_train(const BwdArgs& b, hipStream_t s);
+bool area_train_supports(int n);
+// sot_full_rt_fwd.hip, sot_full_rt_bwd.hip
+hipError_t dispatch_forward_full_rt(int pm, const FwdArgs& a, hipStream_t s);
+hipError_t dispatch_area_full_rt(const FwdArgs& a, hipStream_t s);
+hipError_t dispatch_backward_full_rt(int pm, const BwdArgs& b, hipStream_t s);
+// sot_hip.hip
+int launch_prepare(const float* xpos, const float* ypos, int n, int m, float* sx, float* sy, int* px, int* py, int* ident,
+                   hipStream_t s, bool unit = false);
+int setup_launch(const sot_problem* pr, bool with_grad, void* workspace, size_t workspace_bytes, void* stream, Launch* out);
+int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, float* Q, float* U, float* V, bool quant,
+                void* workspace, size_t workspace_bytes, void* stream, const MeanTail* mean_tail = nullptr);
+int run_backward(const sot_problem* pr, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* gx, float* gy,
+                 void* workspace, size_t workspace_bytes, void* stream, float* row_loss_out = nullptr, bool* fused = nullptr,
+                 const MeanTail* mean_tail = nullptr);
+// sot_csr.hip
+int run_forward_csr(const float* xw, const float* xp, const int64_t* xoff, int64_t x_nnz, const float* yw, const float* yp,
+                    const int64_t* yoff, int64_t y_nnz, int64_t B, int max_n, int max_m, float p, uint32_t flags, float* row_loss,
+                    void* stream);
+// sot_posgrad.hip
+int run_position_grad(const sot_problem* pr, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* gxp, float* gyp,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int run_column_sum(const float* rows, int64_t B, int n, int64_t stride, float* out, void* stream);
+// sot_quantgrad.hip
+int run_quantiles_backward(const sot_problem* pr, const float* gUq, const float* gVq, const float* gQ, const float* gU, const float* gV,
+                           float* gx, float* gy, float* gxp, float* gyp, void* workspace, size_t workspace_bytes, void* stream);
+
+}  // namespace sot

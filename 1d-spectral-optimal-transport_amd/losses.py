@@ -62,7 +62,7 @@ def _hip_domain(*tensors) -> bool:
     return False
 
 
-ROW_SIDE_LIMIT = 16384    # points of ONE side (csrc/sot_hip.hip pick_cfg: at most 1024 threads x 16 points per row)
+ROW_SIDE_LIMIT = 16384    # points of ONE side (csrc/sot_launch.hpp pick_cfg: at most 1024 threads x 16 points per row)
 ROW_POINT_LIMIT = 18000   # n + m of the longest row pair the kernels take for sure (one pair's working set lives in ONE CU's 160 KiB
                           # of LDS; include/sot_hip.h: SOT_ERR_UNSUPPORTED_SIZE beyond ~19000 forward / ~13000 backward)
 
@@ -72,7 +72,7 @@ def _beyond_one_cu(x, y, *positions) -> bool:
     tensors run the package's torch-op composition -- said once -- instead of failing.  No paper configuration comes near."""
     n, m = x.shape[-1], y.shape[-1]
     if any(t is not None and t.ndim >= 2 and not (t.shape[0] > 1 and t.stride(0) == 0) for t in positions):
-        # per-row positions are sorted in LDS on power-of-two arrays (csrc/sot_hip.hip make_layout, rowpos)
+        # per-row positions are sorted in LDS on power-of-two arrays (csrc/sot_rows.hpp make_layout, rowpos)
         n, m = 1 << max(n - 1, 0).bit_length(), 1 << max(m - 1, 0).bit_length()
     wants_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, y) + tuple(positions))
     limit = ROW_POINT_LIMIT if not wants_grad else 12000

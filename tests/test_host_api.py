@@ -142,6 +142,26 @@ def test_stale_library_is_detected_by_content_not_by_mtime(tmp_path, monkeypatch
     assert b.is_stale()                         # digest of other sources -> stale
     (tmp_path / "other.digest").write_text(b.source_digest() + "\n")
     assert not b.is_stale()
+    csrc = os.path.join(ROOT, "1d-spectral-optimal-transport_amd", "csrc")   # every source and header is part of the digest
+    sources = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inc"))]
+    assert len(sources) > 20 and set(sources) <= set(b.DEPS)
+    assert {os.path.join(csrc, src) for _, src in b.OBJECTS} <= set(sources)
+
+
+def test_stamps_variant_of_one_object_links_against_the_product_objects(tmp_path):
+    """build(only=...): a diagnostic library whose named object alone carries the extra flag, the rest being the product's objects.
+    It exports the stamp reader on top of the whole C ABI, and building it leaves the product library and its digest alone."""
+    import sot_amd
+    b = sot_amd.build
+    out = str(tmp_path / "libsot_hip_stamps.so")
+    assert b.build(extra_flags=["-DSOT_STAMPS"], only=("fwd_shared",), out=out) == out
+    handle = ctypes.CDLL(out)
+    for name in ("sot_debug_read_stamps", *sot_amd._native.EXPORTS):
+        assert hasattr(handle, name), name
+    assert not hasattr(ctypes.CDLL(b.LIB), "sot_debug_read_stamps")
+    assert not b.is_stale()
+    with pytest.raises(ValueError):
+        b.build(extra_flags=["-DSOT_STAMPS"], only=("no_such_object",), out=out)
 
 
 def test_cpp_host_path_is_built_in_tree_and_loads_without_a_gpu():

@@ -1,4 +1,4 @@
-"""Diagnostic (build with `python tools/build_variants.py stamps:-DSOT_STAMPS`): where thread 0 of one workgroup of the merge-free
+"""Diagnostic (build with `VARIANT_PART=full_fwd python tools/build_variants.py stamps:-DSOT_STAMPS`): where thread 0 of one workgroup of the merge-free
 p = 1 kernel spends its cycles, phase by phase, summed over its rows in a full-size launch (shares; the stamp fences cost a little)."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

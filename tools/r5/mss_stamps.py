@@ -1,4 +1,4 @@
-"""Phase stamps of the fused MSS kernel (variant library built with tools/build_mss_variant.sh stamps -DMSS_STAMPS):
+"""Phase stamps of the fused MSS kernel (variant library built with VARIANT_PART=mss python tools/build_variants.py stamps:-DMSS_STAMPS):
 SOT_LIB_PATH=tools/ablate_libs/stamps.so python3 tools/r5/mss_stamps.py [clips] [n_fft ...]
 Prints, per workgroup 0..N, the shader clocks between the phase boundaries of its wave 0."""
 import ctypes

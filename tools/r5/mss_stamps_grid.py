@@ -1,5 +1,5 @@
 """Phase stamps of the fused MSS kernel for workgroups spread over the whole grid (one per scale region): variant library built with
-tools/build_mss_variant.sh stamps12 -DMSS_STAMPS -DMSS_STAMP_EVERY=12;  SOT_LIB_PATH=tools/ablate_libs/stamps12.so python3 tools/r5/mss_stamps_grid.py [clips] [every]
+VARIANT_PART=mss python tools/build_variants.py stamps12:-DMSS_STAMPS,-DMSS_STAMP_EVERY=12;  SOT_LIB_PATH=tools/ablate_libs/stamps12.so python3 tools/r5/mss_stamps_grid.py [clips] [every]
 (the clock counters of different CUs are not comparable: durations only)."""
 import ctypes
 import os

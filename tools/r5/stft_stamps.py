@@ -1,4 +1,4 @@
-"""Phase stamps of stft_mag_forward_wavew_kernel (variant library: tools/build_stft_variant.sh stftstamps -DSTFT_STAMPS):
+"""Phase stamps of stft_mag_forward_wavew_kernel (variant library: VARIANT_PART=stft python tools/build_variants.py stftstamps:-DSTFT_STAMPS):
 SOT_LIB_PATH=tools/ablate_libs/stftstamps.so python3 tools/r5/stft_stamps.py [clips]   -> shader clocks of wave 0 of the first workgroups per phase"""
 import ctypes
 import os

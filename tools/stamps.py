@@ -1,8 +1,8 @@
-"""Diagnostic: builds libsot_hip_stamps.so (-DSOT_STAMPS) and prints where one row of workgroup 0 spends
-its cycles (shares, not absolute speed: the stamp fences forbid overlaps the real kernel has)."""
+"""Diagnostic: builds tools/ablate_libs/stamps_<mode>.so (the generic forward object of the chosen mode with -DSOT_STAMPS, the product's objects
+for the rest) and prints where one row of workgroup 0 spends its cycles (shares, not absolute speed: the stamp fences forbid overlaps
+the real kernel has).  The call carries SOT_FLAG_NO_SPECIALIZE, so that the generic kernel runs at every row length."""
 import ctypes
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -14,22 +14,23 @@ from sot_amd import _native as nat  # noqa: E402
 
 mode = sys.argv[1] if len(sys.argv) > 1 else "p1"
 B, N = 8192, int(sys.argv[2]) if len(sys.argv) > 2 else 2048
-lib = os.path.join(ROOT, "gpurun_out", "libsot_hip_stamps.so")
+lib = os.path.join(ROOT, "tools", "ablate_libs", f"stamps_{mode}.so")   # built where the product objects are; run on the GPU box
 os.makedirs(os.path.dirname(lib), exist_ok=True)
-subprocess.run([sot_amd.build.hipcc_path(), *sot_amd.build.HIPCC_FLAGS, "-shared", "-DSOT_STAMPS", "-DSOT_PART=17", "-DSOT_STUB_MISSING_PARTS", "-o", lib,
-                sot_amd.build.SRC], check=True)  # whole-file diagnostic build: shared-position forward + misc only
+if not os.path.exists(lib):
+    sot_amd.build.build(extra_flags=["-DSOT_STAMPS"], only=({"p1": "fwd_shared", "cutoff": "fwd_shared_cutoff"}[mode],), out=lib)
+if not torch.cuda.is_available():
+    sys.exit(f"{lib} is built; run this again on a GPU")
 sot_amd.build.LIB = lib
 nat._lib = None
 h = nat.load(build_if_missing=False)
-from sot_amd.losses import Wasserstein1D  # noqa: E402
 
 dev = torch.device("cuda:0")
-MODES = {"p1": dict(p=1), "cutoff": dict(p=2, square_dist=True, dont_normalize=True, limit_quantile_range=True)}
-mod = Wasserstein1D(**MODES[mode]).to(dev)
+MODES = {"p1": (1.0, nat.FLAG_REQUIRE_SORT), "cutoff": (2.0, nat.FLAG_REQUIRE_SORT | nat.FLAG_SQUARE | nat.FLAG_DONT_NORMALIZE | nat.FLAG_LIMIT_Q)}
+p, flags = MODES[mode]
 x, y = torch.rand(B, N, device=dev), torch.rand(B, N, device=dev)
 pos = torch.linspace(0, 1, N, device=dev)
 for _ in range(5):
-    mod(x, y, x_pos=pos, y_pos=pos)
+    nat.forward_rows(x, y, pos, pos, p, flags | nat.FLAG_NO_SPECIALIZE)
 torch.cuda.synchronize()
 out = (ctypes.c_ulonglong * 64)()
 raw = ctypes.CDLL(lib)

@@ -1,4 +1,4 @@
-"""Diagnostic (build with `python tools/build_variants.py stamps:-DSOT_STAMPS`): where thread 0 of one workgroup of the training-form
+"""Diagnostic (build with `VARIANT_PART=full_bwd python tools/build_variants.py stamps:-DSOT_STAMPS`): where thread 0 of one workgroup of the training-form
 kernel (loss + gradient w.r.t. the estimate, paper mode) spends its cycles, phase by phase, summed over its rows in a full-size launch.
 Usage: python tools/train_stamps.py [B] [N]"""
 import ctypes, os, sys
