@@ -31,7 +31,7 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 16                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 17                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
 FIR_TILE = 1024                  # include/sot_hip.h: SOT_FIR_TILE (outputs per workgroup of the FIR kernel)
 FIR_MIN_TAPS, FIR_MAX_TAPS, FIR_MAX_SAMPLES = 3, 512, 1 << 20   # the FIR kernels' domain (include/sot_hip.h: sot_fir_same_forward)
@@ -73,6 +73,12 @@ EXPORTS = {
     "sot_w1d_position_grad": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp,
                                              ctypes.c_size_t, _vp]),
     "sot_column_sum": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _vp, _vp]),
+    "sot_w1d_mixed_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SotProblem)]),
+    "sot_w1d_mixed_forward": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, ctypes.c_size_t, _vp]),
+    "sot_w1d_mixed_backward": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp,
+                                              ctypes.c_size_t, _vp]),
+    "sot_w1d_mixed_position_grad": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp,
+                                                   ctypes.c_size_t, _vp]),
     "sot_w1d_loss": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_double, ctypes.c_int, ctypes.c_float, _vp, _vp,
                                     _vp, _vp, ctypes.c_size_t, _vp]),
     "sot_w1d_quantiles": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp,
@@ -596,6 +602,97 @@ def position_grads(x, y, xpos, ypos, p, flags, grad_row, need_x=True, need_y=Tru
             tot = torch.empty(width, dtype=torch.float32, device=dev)
             check(lib.sot_column_sum(rows.data_ptr(), B, width, width, tot.data_ptr(), stream_ptr(dev)), p)
             out.append(tot)
+    return out
+
+
+# ---- mixed supports (include/sot_hip.h: sot_w1d_mixed_*): one side on a shared 1-D grid, the other with [B, K] positions per row ----
+MIXED_ROW_SIDE_LIMIT = 2048    # points of the per-row side (csrc/sot_mixed.hip: kMixedMaxRowSide)
+MIXED_POINT_LIMIT = 12000      # pow2(n) + pow2(m) that always fits the kernels' gradient layout (include/sot_hip.h)
+
+
+def mixed_problem(x, y, xpos, ypos, p, flags, plan=None) -> SotProblem:
+    """The sot_problem of a mixed call: exactly one of xpos / ypos is 1-D.  plan: a PositionPlan of (grid, grid) for the shared side
+    (its x half is used, whichever side is shared) or None -- the call then plans the grid in its workspace when it has to sort."""
+    B, n = x.shape
+    m = y.shape[1]
+    x_shared = xpos.ndim == 1
+    assert x_shared != (ypos.ndim == 1), "mixed supports: exactly one side has 1-D positions"
+    pr = SotProblem()
+    pr.x, pr.y = x.data_ptr(), y.data_ptr()
+    pr.B, pr.n, pr.m = B, n, m
+    pr.x_row_stride = x.stride(0) if B > 1 else n
+    pr.y_row_stride = y.stride(0) if B > 1 else m
+    pr.p, pr.flags = float(p), int(flags)
+    pr.xpos, pr.ypos = xpos.data_ptr(), ypos.data_ptr()
+    pr.xpos_row_stride = 0 if x_shared else (xpos.stride(0) if B > 1 else n)
+    pr.ypos_row_stride = 0 if not x_shared else (ypos.stride(0) if B > 1 else m)
+    pr.xperm = pr.yperm = pr.perm_is_identity = None
+    pr.row_perm_out = pr.row_perm_in = None
+    if plan is not None:
+        plan.use_on_current_stream(x.device)
+        pr.perm_is_identity = plan.ident.data_ptr()   # both flags describe the one grid the plan was made of
+        if x_shared:
+            pr.xpos, pr.xperm = plan.xpos_sorted.data_ptr(), plan.xperm.data_ptr()
+        else:
+            pr.ypos, pr.yperm = plan.xpos_sorted.data_ptr(), plan.xperm.data_ptr()
+    return pr
+
+
+def _mixed_workspace(lib, pr, device):
+    nbytes = int(lib.sot_w1d_mixed_workspace_bytes(ctypes.byref(pr)))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def _grad_row_arg(grad_row, B):
+    g = grad_row.contiguous()
+    stride = 0 if g.numel() == 1 else 1
+    if stride == 1 and g.numel() != B:
+        raise RuntimeError(f"grad_row has {g.numel()} elements for {B} rows")
+    return g, stride
+
+
+def mixed_forward_rows(x, y, xpos, ypos, p, flags, plan=None) -> torch.Tensor:
+    """row_loss[B] = W_p^p per row for a shared grid against per-row positions (sot_w1d_mixed_forward)."""
+    lib = load()
+    dev = x.device
+    row_loss = torch.empty(x.shape[0], dtype=torch.float32, device=dev)
+    pr = mixed_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = _mixed_workspace(lib, pr, dev)
+    with _on_device(dev):
+        rc = lib.sot_w1d_mixed_forward(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return row_loss
+
+
+def mixed_backward_rows(x, y, xpos, ypos, p, flags, grad_row, need_gx=True, need_gy=True, plan=None, grad_scale=1.0):
+    """Weight gradients of both sides (sot_w1d_mixed_backward); grad_row as in backward_rows."""
+    lib = load()
+    dev = x.device
+    gx = torch.empty(x.shape, dtype=torch.float32, device=dev) if need_gx else None
+    gy = torch.empty(y.shape, dtype=torch.float32, device=dev) if need_gy else None
+    pr = mixed_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = _mixed_workspace(lib, pr, dev)
+    g, stride = _grad_row_arg(grad_row, x.shape[0])
+    with _on_device(dev):
+        rc = lib.sot_w1d_mixed_backward(ctypes.byref(pr), g.data_ptr(), stride, float(grad_scale), _ptr(gx), _ptr(gy), _ptr(ws),
+                                        ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return gx, gy
+
+
+def mixed_position_grad(x, y, xpos, ypos, p, flags, grad_row, plan=None, grad_scale=1.0) -> torch.Tensor:
+    """Gradient w.r.t. the per-row side's positions, [B, K] in the caller's column order (sot_w1d_mixed_position_grad)."""
+    lib = load()
+    dev = x.device
+    rowpos = ypos if xpos.ndim == 1 else xpos
+    out = torch.empty(rowpos.shape, dtype=torch.float32, device=dev)
+    pr = mixed_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = _mixed_workspace(lib, pr, dev)
+    g, stride = _grad_row_arg(grad_row, x.shape[0])
+    with _on_device(dev):
+        rc = lib.sot_w1d_mixed_position_grad(ctypes.byref(pr), g.data_ptr(), stride, float(grad_scale), out.data_ptr(), _ptr(ws),
+                                             ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
     return out
 
 

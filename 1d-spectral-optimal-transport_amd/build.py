@@ -26,6 +26,7 @@ OBJECTS = (
     ("csr", "sot_csr.hip"),                              # CSR (ragged) forward
     ("posgrad", "sot_posgrad.hip"),                      # position gradient, column sum
     ("quantgrad", "sot_quantgrad.hip"),                  # gradient of the return_quantiles tensors
+    ("mixed", "sot_mixed.hip"),                          # mixed supports: a shared grid against per-row positions
     ("stft", "sot_stft.hip"),                            # the STFT-magnitude producer
     ("osc", "sot_osc.hip"),                              # the oscillator bank
     ("mss", "sot_mss.hip"),                              # MSSLoss with its gradient in two launches

@@ -166,6 +166,97 @@ class _RowLoss(torch.autograd.Function):
         return gx, gy, gxp, gyp, None, None, None
 
 
+MIXED_ROUTE = True   # module switch (tests and tools/bench_mixed.py compare both routes): False = mixed supports are materialised as before
+
+
+def _is_shared_row(t) -> bool:
+    """One position row for every batch row: a 1-D tensor, or a stride-0 expansion of one row (losses.py:167-170)."""
+    if t.ndim == 1:
+        return True
+    lead = [(size, stride) for size, stride in zip(t.shape[:-1], t.stride()[:-1]) if size > 1]
+    return bool(lead) and all(stride == 0 for _, stride in lead)
+
+
+def mixed_route_applies(x, y, xpos, ypos, return_quantiles=False) -> bool:
+    """Does a call take the native mixed-supports route (sot_w1d_mixed_*: a shared grid on one side, [batch, (time,) K] positions per row
+    on the other, nothing materialised)?  A function of shapes, strides, requires_grad, the grad mode and MIXED_ROUTE alone -- no device is
+    touched.  Everything else keeps the materialising route: both sides of one kind, return_quantiles (the quantile kernels have no mixed
+    form), a shared grid that itself needs a gradient (the mixed position gradient covers the per-row side only), a per-row side of more
+    than nat.MIXED_ROW_SIDE_LIMIT points, and pairs beyond the kernels' LDS budget (include/sot_hip.h)."""
+    if not MIXED_ROUTE or return_quantiles:
+        return False
+    x_shared = _is_shared_row(xpos)
+    if x_shared == _is_shared_row(ypos):
+        return False
+    grid, rows = (xpos, ypos) if x_shared else (ypos, xpos)
+    if rows.ndim not in (2, 3) or (torch.is_grad_enabled() and grid.requires_grad):
+        return False
+    n, m = x.shape[-1], y.shape[-1]
+    k = m if x_shared else n
+    pow2 = lambda v: 1 << max(v - 1, 0).bit_length()   # noqa: E731
+    return 1 <= k <= nat.MIXED_ROW_SIDE_LIMIT and pow2(n) + pow2(m) <= nat.MIXED_POINT_LIMIT
+
+
+def _marshal_mixed(x, y, xpos, ypos):
+    """2-D weight rows, the shared side as its one 1-D row, the per-row side as contiguous [rows, K] (mixed_route_applies holds)."""
+    x = nat.rows_view(x.reshape(-1, x.shape[-1]))
+    y = nat.rows_view(y.reshape(-1, y.shape[-1]))
+    if x.shape[0] != y.shape[0]:
+        raise RuntimeError(f"row count mismatch: {x.shape[0]} vs {y.shape[0]}")
+    if xpos.shape[-1] != x.shape[1] or ypos.shape[-1] != y.shape[1]:
+        raise RuntimeError("positions and weights must have the same number of features")
+
+    def one_side(pos):
+        if _is_shared_row(pos):
+            return pos.reshape(-1, pos.shape[-1])[0].contiguous() if pos.ndim > 1 else pos.contiguous()
+        pos = pos.reshape(-1, pos.shape[-1]).contiguous()
+        if pos.shape[0] != x.shape[0]:
+            raise RuntimeError("per-row positions must have one row per weight row")
+        return pos
+    return x, y, one_side(xpos), one_side(ypos)
+
+
+class _MixedRowLoss(torch.autograd.Function):
+    """rows[B] = W_p^p per pair with ONE side on a shared grid and the other on per-row positions (sot_w1d_mixed_forward): the shared row
+    is neither expanded nor sorted per row.  Backward: weight gradients of both sides (sot_w1d_mixed_backward) and the position gradient
+    of the per-row side (sot_w1d_mixed_position_grad); the kernels sort the short per-row side again.  plan: the shared grid's
+    PositionPlan (or None without require_sort).  The shared grid receives no gradient here (mixed_route_applies sends such calls to
+    the materialising route)."""
+
+    @staticmethod
+    def forward(ctx, x, y, xpos, ypos, p, flags, plan):
+        rows = nat.mixed_forward_rows(x, y, xpos, ypos, p, flags, plan)
+        ctx.save_for_backward(x, y, xpos, ypos)
+        ctx.p, ctx.flags, ctx.plan = p, flags, plan
+        return rows
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        x, y, xpos, ypos = ctx.saved_tensors
+        x_shared = xpos.ndim == 1
+        if ctx.needs_input_grad[2 if x_shared else 3]:
+            raise RuntimeError("sot_amd: the mixed-supports route has no gradient for the shared grid")
+        gx = gy = gpos = None
+        g = grad_rows.float()
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gx, gy = nat.mixed_backward_rows(x, y, xpos, ypos, ctx.p, ctx.flags, g, need_gx=ctx.needs_input_grad[0],
+                                             need_gy=ctx.needs_input_grad[1], plan=ctx.plan)
+        if ctx.needs_input_grad[3 if x_shared else 2]:
+            gpos = nat.mixed_position_grad(x, y, xpos, ypos, ctx.p, ctx.flags, g, plan=ctx.plan)
+        return gx, gy, (None if x_shared else gpos), (gpos if x_shared else None), None, None, None
+
+
+def _mixed_row_losses(x, y, xpos, ypos, p, flags, plans):
+    """The mixed-supports route behind Wasserstein1D.row_losses and wasserstein_1d; plans: the caller's _PlanCache (the shared grid is
+    planned once per tensor version, as on the all-shared route)."""
+    x, y, xpos, ypos = _marshal_mixed(x, y, xpos, ypos)
+    grid = xpos if xpos.ndim == 1 else ypos
+    plan = plans.get(grid, grid) if (flags & nat.FLAG_REQUIRE_SORT) else None
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)):
+        return _MixedRowLoss.apply(x, y, xpos, ypos, float(p), flags, plan)
+    return nat.mixed_forward_rows(x, y, xpos, ypos, float(p), flags, plan)
+
+
 class _Quantiles(torch.autograd.Function):
     """The five return_quantiles tensors (uq, vq, Q, U, V: losses.py:198-201, 299-300) with their vector-Jacobian product
     (sot_w1d_quantiles_backward: one HIP kernel, one merge walk for weights and positions).  In the reference these tensors come from
@@ -329,6 +420,10 @@ def wasserstein_1d(u_values, v_values, u_weights=None, v_weights=None, p=1, requ
         return tp.transport_rows(u_values, v_values, u_weights, v_weights, p=p, require_sort=require_sort,
                                  return_quantiles=return_quantiles, limit_quantile_range=limit_quantile_range)
 
+    if mixed_route_applies(u_weights, v_weights, u_values, v_values, return_quantiles):
+        flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
+        return _mixed_row_losses(u_weights, v_weights, u_values, v_values, p, flags, _functional_plans)
+
     # stride-0 expanded positions (losses.py:167-170) are passed down as one shared row
     def shared_row(t):
         return t[0] if (t.ndim == 2 and t.shape[0] > 1 and t.stride(0) == 0) else t
@@ -453,6 +548,14 @@ class Wasserstein1D(torch.nn.Module):
         assert self.p >= 1, f"The OT loss is only valid for p>=1, {self.p} was given"  # losses.py:271
         return (self.fixed_x if x_pos is None else x_pos), (self.fixed_x if y_pos is None else y_pos)
 
+    def _flag_word(self, kwargs):
+        dont_normalize = bool(kwargs.get("dont_normalize", False) or self.dont_normalize)
+        limit_q = bool(kwargs.get("limit_quantile_range", False) or self.limit_quantile_range)
+        flags = _flags(self.square_dist, dont_normalize, limit_q, self.require_sort)
+        if getattr(self, "tie_free_gradient", False):
+            flags |= nat.FLAG_TIE_FREE_GRADIENT
+        return flags
+
     def _marshal(self, x, y, x_pos, y_pos, kwargs):
         """float32 GPU tensors -> what the native calls take: 2-D rows, positions, flag word, position plan."""
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
@@ -466,12 +569,7 @@ class Wasserstein1D(torch.nn.Module):
         if y_pos_.ndim == 3:
             y_pos_ = y_pos_.reshape(-1, y_pos_.shape[-1])
 
-        dont_normalize = bool(kwargs.get("dont_normalize", False) or self.dont_normalize)
-        limit_q = bool(kwargs.get("limit_quantile_range", False) or self.limit_quantile_range)
-        flags = _flags(self.square_dist, dont_normalize, limit_q, self.require_sort)
-        if getattr(self, "tie_free_gradient", False):
-            flags |= nat.FLAG_TIE_FREE_GRADIENT
-
+        flags = self._flag_word(kwargs)
         x, y, x_pos_, y_pos_ = _prepare(x, y, x_pos_, y_pos_, checked=True)
         plan = self._plans.get(x_pos_, y_pos_) if (self.require_sort and x_pos_.ndim == 1) else None
         return x, y, x_pos_, y_pos_, flags, plan, original_shape
@@ -492,11 +590,14 @@ class Wasserstein1D(torch.nn.Module):
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
         if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
             return self._torch_forward(x, y, x_pos_, y_pos_, kwargs, rows_only=True)
-        x, y, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
-        if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, x_pos_, y_pos_)):
-            loss = _RowLoss.apply(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
+        if mixed_route_applies(x, y, x_pos_, y_pos_):   # a shared grid against per-row positions: nothing is materialised
+            loss = _mixed_row_losses(x, y, x_pos_, y_pos_, self.p, self._flag_word(kwargs), self._plans)
         else:
-            loss = nat.forward_rows(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
+            x, y, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
+            if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, x_pos_, y_pos_)):
+                loss = _RowLoss.apply(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
+            else:
+                loss = nat.forward_rows(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
         if self.hinge:
             loss = torch.nn.functional.relu(loss - kwargs.get("hinge", 0.0))
         return loss
@@ -550,7 +651,7 @@ class Wasserstein1D(torch.nn.Module):
 
         original_shape = x.shape[:-1]
         dims = kwargs.get("dims", None)
-        if dims is None and not self.hinge:
+        if dims is None and not self.hinge and not mixed_route_applies(x, y, x_pos_, y_pos_):
             # default reduction: forward and the mean over every row (losses.py:211) in one native call
             x2, y2, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
             grad_on = torch.is_grad_enabled()

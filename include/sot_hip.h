@@ -27,9 +27,9 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 16   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+#define SOT_ABI_VERSION 17   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
                               * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
-                              *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics) */
+                              *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics; 17: sot_w1d_mixed_*) */
 
 typedef enum sot_status {
     SOT_OK = 0,
@@ -275,6 +275,37 @@ int sot_w1d_quantiles_backward(const sot_problem *prob, const float *grad_uq, co
 int sot_w1d_position_grad(const sot_problem *prob, const float *grad_row, int64_t grad_row_stride, float grad_scale,
                           float *grad_xpos /* [B,n] or NULL */, float *grad_ypos /* [B,m] or NULL */,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Mixed supports (ABI 17; csrc/sot_mixed.hip): ONE measure lives on a position row shared by every batch row, the other has
+ * positions of its own per row -- exactly one of prob->xpos_row_stride / prob->ypos_row_stride is 0 (Wasserstein1D.forward accepts the
+ * two kinds side by side, losses.py:162-170).  The parametric use: a dense target spectrum on the STFT bin grid against a model's line
+ * spectrum, K partials per frame with their amplitudes as weights and their frequencies as positions.  Semantics per row are those of
+ * sot_w1d_forward / sot_w1d_backward / sot_w1d_position_grad on the same problem with the shared row repeated for every batch row
+ * (same flags, same tie convention; x's mass stays the divisor under SOT_FLAG_DONT_NORMALIZE whichever side is shared), without that
+ * copy: the shared side goes through the position plan once per call and is staged once per workgroup, only the per-row side is
+ * sorted per row (stable, in the kernel; the gradient kernels sort again).
+ * Plan contract of the shared side with SOT_FLAG_REQUIRE_SORT, as for shared positions elsewhere: either the plan is passed --
+ * perm_is_identity != NULL, the shared side's xpos / ypos holds the SORTED positions sot_prepare_positions produced, its xperm / yperm the
+ * permutation and perm_is_identity[0] (x shared) / [1] (y shared) its flag; the other side's plan fields are not read -- or `workspace`
+ * holds sot_w1d_mixed_workspace_bytes() bytes and the call plans the row itself.  row_perm_out / row_perm_in are not used.
+ * Domain: the per-row side has 1 ... 2048 points, and the pair fits the generic per-row-position kernels' gradient layout in one CU's
+ * LDS with 8 bytes per thread to spare (csrc/sot_mixed.hip: mixed_domain, from make_layout; pow2(n) + pow2(m) <= 12 000 always fits).
+ * One domain for the three calls.
+ * Status, all decided on the host before any pointer is followed or anything is enqueued: SOT_ERR_NULL_POINTER (prob, an output, and with
+ * B > 0 x / y / xpos / ypos, a plan without the shared side's permutation, a missing workspace); SOT_ERR_INVALID_P; SOT_ERR_BAD_SHAPE for
+ * B < 0, n < 1, m < 1, bad strides, and for both position strides 0 or both non-zero; SOT_ERR_UNSUPPORTED_SIZE outside the domain;
+ * SOT_ERR_WORKSPACE.  B == 0: SOT_OK, nothing is touched.
+ * sot_w1d_mixed_backward: grad_x [B, n] and / or grad_y [B, m], either may be NULL (both: SOT_OK, nothing is enqueued).
+ * sot_w1d_mixed_position_grad: grad_pos [B, K] for the PER-ROW side only, in the caller's column order (a shared grid that needs a
+ * gradient takes sot_w1d_position_grad on expanded positions).  grad_row / grad_row_stride / grad_scale as in sot_w1d_backward.
+ * One kernel per call (plus the plan kernel when the call plans), deterministic (no atomics), enqueue-only, graph-capturable. */
+size_t sot_w1d_mixed_workspace_bytes(const sot_problem *prob);   /* 0 for a problem the calls refuse, and when no workspace is needed */
+int sot_w1d_mixed_forward(const sot_problem *prob, float *row_loss /* [B] */, void *workspace, size_t workspace_bytes, void *stream);
+int sot_w1d_mixed_backward(const sot_problem *prob, const float *grad_row, int64_t grad_row_stride, float grad_scale,
+                           float *grad_x /* [B,n] or NULL */, float *grad_y /* [B,m] or NULL */,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int sot_w1d_mixed_position_grad(const sot_problem *prob, const float *grad_row, int64_t grad_row_stride, float grad_scale,
+                                float *grad_pos /* [B,K]: the per-row side */, void *workspace, size_t workspace_bytes, void *stream);
 
 /* out[c] = sum_r rows[r * row_stride + c], c < n, in a fixed order with fp64 accumulation. */
 int sot_column_sum(const float *rows, int64_t B, int32_t n, int64_t row_stride, float *out /* [n] */, void *stream);
