@@ -13,8 +13,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # (object name, source): one translation unit each, compiled in parallel and linked into one shared library; the slowest first.
 OBJECTS = (
-    ("full_fwd", "sot_full_fwd.hip"),                    # full-row kernels (sot_forward_full.inc): compile-time row lengths, forward
-    ("full_bwd", "sot_full_bwd.hip"),                    #   ... backward and the merge-free training form
+    ("full_fwd", "sot_full_fwd.hip"),                    # full-row kernels (sot_full_fwd.hpp): compile-time row lengths, forward
+    ("full_bwd", "sot_full_bwd.hip"),                    #   ... (sot_full_bwd.hpp) backward and the merge-free training form
     ("full_rt_fwd", "sot_full_rt_fwd.hip"),              #   ... run-time row lengths, forward
     ("full_rt_bwd", "sot_full_rt_bwd.hip"),              #   ... run-time row lengths, backward
     ("fwd_shared", "sot_fwd_shared.hip"),                # generic kernels (sot_rows.hpp): forward, shared positions, no cutoff

@@ -7,13 +7,7 @@ namespace sot {
 template <int G, int CPT, int PM, bool LIM>
 static hipError_t launch_forward_csr(const FwdArgs& a, size_t lds, int64_t want, int block, hipStream_t s)
 {
-    auto kern = sot_forward_kernel<G, CPT, true, false, PM, LIM, false, true>;
-    static GridCache cache;  // per instantiation (function-local static: thread-safe initialisation)
-    const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = persistent_grid(want, grid_cap);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent<sot_forward_kernel<G, CPT, true, false, PM, LIM, false, true>>(a, lds, want, block, s);
 }
 
 template <int G, int CPT>

@@ -1,5 +1,4 @@
-// sot_dispatch.hpp -- run-time -> compile-time dispatch of the generic row kernels (sot_rows.hpp): the launch templates with their
-// per-instantiation grid caches and the switches over geometry, p, cutoff and load width.  The objects that include it hold nothing
+// sot_dispatch.hpp -- run-time -> compile-time dispatch of the generic row kernels (sot_rows.hpp): the launch templates and the switches over geometry, p, cutoff and load width.  The objects that include it hold nothing
 // but explicit instantiations: sot_fwd_shared.hip, sot_fwd_shared_cutoff.hip, sot_fwd_rowpos.hip, sot_bwd_shared.hip, sot_bwd_rowpos.hip.
 #pragma once
 #include "sot_launch.hpp"
@@ -9,13 +8,7 @@ namespace sot {
 template <int G, int CPT, bool ROWPOS, bool QUANT, int PM, bool LIM, bool VEC, int SQM = 2>
 static hipError_t launch_forward(const FwdArgs& a, size_t lds, int64_t want, int block, hipStream_t s)
 {
-    auto kern = sot_forward_kernel<G, CPT, ROWPOS, QUANT, PM, LIM, VEC, false, SQM>;
-    static GridCache cache;  // per instantiation (function-local static: thread-safe initialisation)
-    const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = persistent_grid(want, grid_cap);
-    (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, a);
-    return hipGetLastError();
+    return launch_persistent<sot_forward_kernel<G, CPT, ROWPOS, QUANT, PM, LIM, VEC, false, SQM>>(a, lds, want, block, s);
 }
 
 template <int G, int CPT, bool ROWPOS, bool LIM, bool VEC>
@@ -82,13 +75,7 @@ hipError_t dispatch_forward(const LaunchCfg& c, bool quant, int pm, bool vec, co
 template <int G, int CPT, bool ROWPOS, int PM, bool LIM, bool VEC>
 static hipError_t launch_backward(const BwdArgs& b, size_t lds, int64_t want, int block, hipStream_t s)
 {
-    auto kern = sot_backward_kernel<G, CPT, ROWPOS, PM, LIM, VEC>;
-    static GridCache cache;  // per instantiation (function-local static: thread-safe initialisation)
-    const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = persistent_grid(want, grid_cap);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, b);
-    return hipGetLastError();
+    return launch_persistent<sot_backward_kernel<G, CPT, ROWPOS, PM, LIM, VEC>>(b, lds, want, block, s);
 }
 
 template <int G, int CPT, bool ROWPOS, bool LIM, bool VEC>

@@ -1,6 +1,6 @@
 // sot_full_bwd.hip -- full-row backward kernels for compile-time row lengths, and the merge-free training form;
-// the kernel and launch templates are in sot_forward_full.inc.
-#include "sot_forward_full.inc"
+// the kernel and launch templates are in sot_full_bwd.hpp.
+#include "sot_full_bwd.hpp"
 
 namespace sot {
 
@@ -25,7 +25,7 @@ bool area_train_supports(int n) { return n == 512 || n == 1024 || n == 2048 || n
 // Rows per workgroup of the y-only (training) kernel for 2048-bin rows.  Without gradient slots for U two rows and the shared
 // position copy take 68.7 KB: two workgroups = four rows per CU instead of three (one row with U slots + positions: 50.9 KB).
 // Measured at 8192 x 2048, paper mode: 79.7 instead of 81.5 us.
-hipError_t dispatch_backward_full(const LaunchCfg&, int pm, const BwdArgs& b, hipStream_t s)
+hipError_t dispatch_backward_full(int pm, const BwdArgs& b, hipStream_t s)
 {
     switch (b.f.n) {
         case 512: return dispatch_backward_full_g<64, 8, 4>(pm, b, s);   // (the slim layout adds a fourth workgroup per CU here too: 64.5 vs 65.0 us, nothing)

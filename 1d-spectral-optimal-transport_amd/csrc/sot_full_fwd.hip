@@ -1,6 +1,6 @@
 // sot_full_fwd.hip -- full-row forward kernels for compile-time row lengths, and which row lengths the full-row kernels take;
-// the kernel and launch templates are in sot_forward_full.inc.
-#include "sot_forward_full.inc"
+// the kernel and launch templates are in sot_full_fwd.hpp.
+#include "sot_full_fwd.hpp"
 
 namespace sot {
 
@@ -60,7 +60,7 @@ bool forward_full_supports(int n, bool aligned16)
 
 // The caller (run_forward) guarantees: shared positions, n == m with forward_full_supports(n, ...), p in {1, 2}, not
 // pre-normalised.  LDS size, block size and grid are this kernel's own (shared-position layout).
-hipError_t dispatch_forward_full(const LaunchCfg&, int pm, const FwdArgs& a, size_t, int64_t, int, hipStream_t s)
+hipError_t dispatch_forward_full(int pm, const FwdArgs& a, hipStream_t s)
 {
     switch (a.n) {
         case 512: return dispatch_forward_full_g<64, 8, 4>(pm, a, s);

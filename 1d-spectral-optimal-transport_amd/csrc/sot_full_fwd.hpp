@@ -1,0 +1,601 @@
+// sot_full_fwd.hpp -- forward kernels of the full-row family (compile-time geometries) with their launch and dispatch templates,
+// namespace sot: the merge forward, the merge-free p = 1 forward (area) and their two-rows-per-wave forms.  Included by the objects
+// that instantiate them: sot_full_fwd.hip (compile-time row lengths) and sot_full_rt_fwd.hip (run-time row lengths), where the
+// non-template dispatch functions live (dispatch_forward_full, dispatch_area_full, ...).  The backward side is sot_full_bwd.hpp.
+//
+// Full-row forward kernel: the row pipeline of sot_forward_kernel for row lengths known at compile time: rows that fill
+// their geometry exactly (n == m == G*CPT = 512, 2048 or 8192; 16-B aligned rows) and the paper's 257 / 513 / 1025 bins
+// (n_fft 512 / 1024 / 2048; any alignment; template parameter NX); shared positions, p in {1, 2}, not pre-normalised.
+// Every length, the LDS layout, the ATen summation plan and the merge-walk trip count are compile-time
+// constants: no per-element bounds predicates, no generic chunk loops, LDS offsets folded into the
+// instructions, and the walk advances two LDS byte offsets instead of recomputing addresses from indices.
+// Same arithmetic, operation for operation, as the generic kernel: for 512 / 2048 / 8192 bins row losses and gradients
+// are bit-identical (tests/test_gpu_parity.py::test_full_row_kernel_matches_generic); for 257 / 513 / 1025 bins the
+// thread geometry differs from the generic kernel's, so sums are associated differently (agreement to ~1e-7).
+// A workgroup holds ROWS rows (one row group of G threads each) and ONE copy of the support positions, placed behind
+// the row regions with the same internal offsets, so that "position of the element at LDS offset o of row r" is
+// o + (ROWS - r) * rowf: a compile-time immediate per row group (512-bin rows: four rows per 256-thread workgroup).
+// Reference semantics: losses.py:172-196, :271-313, :214-220; utils.py:135-142.
+#pragma once
+#include "sot_full_common.hpp"
+
+namespace sot {
+
+// the one-wave-per-row forward kernels of 1025-bin rows (17 elements per thread): 152 / 154 VGPRs = three waves per SIMD; held to four
+// (128 VGPRs, spills): 16384 x 1025 paper mode 41.5 -> 77.4 us, p = 1 28.8 -> 47.0 us -- left alone
+constexpr int kFwd17MinWaves = 1;
+
+constexpr int kFwd1025OneWaveRows = 6144;   // batches of at least this many 1025-bin rows: one wave per row in the forward kernel
+constexpr int kRt1024OneWaveRows = 8192;    // the same for run-time lengths on the 1024-point geometry (16 elements per thread)
+
+// E steps of the merge for one thread (losses.py:295-313) in "loser" form: (w, wp) is the head fetched last, (r, rp) the
+// head that lost the previous comparison; the smaller one is consumed and only ITS stream is read again, so the fetched
+// level and position become the new (w, wp) without any select: 10 VALU per step instead of 15.  Equal heads may be
+// consumed in either order (w first here, U first in the canonical stable order): the pair of heads is the same either
+// way, so the consumed level, its width and its cost factor are identical, and the second member of a tie has zero
+// width -- the accumulated sum is bit-identical to the canonical order's.
+// ou / ov: 32-bit LDS byte addresses of the two heads; the position of the element at address o is at o + POFF4.
+// (Carrying generic pointers instead costs one more select per step: 3.6 % slower.)
+template <int E, int PM, bool LIM, uint32_t POFF4>
+__device__ __forceinline__ float merge_walk_full(uint32_t ou, uint32_t ov, bool first, float p)
+{
+    float w = lds_load(ou), wp = lds_load(ou + POFF4);
+    float r = lds_load(ov), rp = lds_load(ov + POFF4);
+    float qprev = fmaxf(lds_load(ou - 4u), lds_load(ov - 4u));
+    if (first) qprev = 0.0f;  // Q_0 := 0 (the pad of losses.py:301)
+    uint32_t pw = ou + 4u, pr = ov + 4u;  // next unread element of w's / r's stream
+    float acc = 0.0f;
+#pragma unroll SOT_FULL_WALK_UNROLL
+    for (int s2 = 0; s2 < E; ++s2) {
+        const bool c = w <= r;
+        const float q = c ? w : r;
+        const float cost = transport_cost<PM>(wp, rp, p);
+        float delta = q - qprev;
+        if (LIM && q > 1.0f) delta = 0.0f;
+        acc = fmaf(delta, cost, acc);  // fused: no worse than the reference's separate rounding
+        qprev = q;
+        const uint32_t nx = c ? pw : pr;
+        pr = c ? pr : pw;
+        pw = nx + 4u;
+        r = c ? r : w;
+        rp = c ? rp : wp;
+        w = lds_load(nx);
+        wp = lds_load(nx + POFF4);
+    }
+    return acc;
+}
+
+// staged LDS indices of the CPT elements thread t owns in sorted order on a permuted shared grid (see full_build_cdfs: psx / psy)
+template <int G, int CPT, int ROWS, int NX>
+__device__ __forceinline__ void owner_perm_slots(const FwdArgs& a, const int* perm, int t, int (&ps)[CPT])
+{
+    using Geo = FullGeo<G, CPT, ROWS, false, NX>;
+    constexpr int N = Geo::N;
+    const int nreal = Geo::RT ? a.n : N;
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+        const int sx = (t * CPT + k < nreal) ? perm[t * CPT + k] : N + 1;
+        ps[k] = Geo::SWZ ? (sx ^ (((sx >> 5) & 1) << 2)) : sx;
+    }
+}
+
+// Geometry experiments on 8192 x 2048 (all slower than one 256-thread row per workgroup, 4 workgroups per CU, 44.8 us):
+// two rows per 512-thread workgroup sharing the positions: 46.5 us at the same 4 rows per CU; held to 96 VGPRs 52.3 us,
+// to 80 VGPRs (6 rows per CU, 26 dwords spilled) 74 us; 512 threads x 4 elements per row 53-54 us.
+constexpr int kFwdMinWaves = 1;
+// (The run-time-length kernel of the 4096-point geometry came out at 129 VGPRs: one 512-thread workgroup per CU instead of the two its LDS allows;
+//  held to 128 -- four waves per SIMD -- 4096 x 4000 paper mode: see profiles/r4p_segmented_sort.txt, "register steps".)
+constexpr int kRt512MinWaves = 4;
+
+// RP (round 6): PER-ROW positions whose sort permutations are handed in (a.perm_in: [B, 2 N] uint16, written by sot_rowpos_sort_kernel or an earlier
+// forward): every row brings its own positions -- loaded coalesced, staged in the U / V regions, gathered through the permutation into the
+// position copy behind the row region -- and its weights are read through the same permutation (the psx / psy path of a permuted shared grid).
+// One row per workgroup only (the position copy is the row's own), rows that fill their geometry (NX == 0).
+template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX = 0, bool RP = false>
+__global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? kRt512MinWaves : (CPT == 17) ? kFwd17MinWaves : kFwdMinWaves) void sot_forward_full_kernel(const FwdArgs a)
+{
+    static_assert(!RP || (ROWS == 1 && NX == 0 && CPT == 8), "per-row positions: one row per workgroup, rows that fill the 8-element geometry");
+    using Geo = FullGeo<G, CPT, ROWS, false, NX>;
+    constexpr FullLayout L = Geo::L;
+    constexpr int N = Geo::N, NW = Geo::NW, E = Geo::E, GA = Geo::GA, PAD = Geo::PAD;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int64_t row_step = (int64_t)gridDim.x * ROWS;
+    int64_t row0 = (int64_t)blockIdx.x * ROWS;
+    float rx[CPT], ry[CPT];
+    FullCtx cm = full_setup<G, CPT, ROWS, false, NX, RP>(a, smem);
+    if constexpr (RP) { cm.x_ident = false; cm.y_ident = false; }
+    const FullCtx c = cm;
+    if constexpr (NW == 1) __syncthreads();   // the position copy is shared by the row groups, whose rows then run wave-synchronised
+    const int rg = c.rg, t = c.t, lane = c.lane, wv = c.wv;
+    float* const V = c.V; float* const red = c.red;
+    const float* const Uw = c.Uw;
+    if (row0 < a.B) {
+        const int64_t r = min(row0 + rg, a.B - 1);
+        fetch_row<G, CPT, NX>(a.x + r * a.xs, a.y + r * a.ys, t, a.n, rx, ry);
+    }
+
+#ifdef SOT_STAMPS
+    unsigned long long sbuf[16] = {};
+    unsigned long long* const sacc = (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2) ? sbuf : nullptr;
+#else
+    constexpr unsigned long long* sacc = nullptr;
+#endif
+    // (2 CPT registers for the whole row loop: only where they do not cost a wave per SIMD -- the 17-element one-wave rows keep the per-row lookup)
+    constexpr bool HOIST_PERM = CPT <= 9;
+    int psx[HOIST_PERM ? CPT : 1] = {}, psy[HOIST_PERM ? CPT : 1] = {};
+    if constexpr (HOIST_PERM && !RP) {
+        if (!c.x_ident) owner_perm_slots<G, CPT, ROWS, NX>(a, a.xperm, t, psx);
+        if (!c.y_ident) owner_perm_slots<G, CPT, ROWS, NX>(a, a.yperm, t, psy);
+    }
+    for (; row0 < a.B; row0 += row_step) {
+        const int64_t row = row0 + rg;
+        const bool valid = row < a.B;
+        const bool more = row0 + row_step < a.B;
+        const int64_t rn = min(row0 + row_step + rg, a.B - 1);
+        float wx[CPT], wy[CPT], cu[CPT], cv[CPT];
+        float Sx, Sy;
+#ifdef SOT_STAMPS
+        if (sacc != nullptr) sacc[15] = __builtin_readcyclecounter();
+#endif
+        if constexpr (RP) {
+            int ix[CPT], iy[CPT];
+            rowpos_row_setup<G, CPT, ROWS, false, NX>(a, c, min(row, a.B - 1), ix, iy, psx, psy);
+        }
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
+                                                     more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc, HOIST_PERM ? psx : nullptr,
+                                                     HOIST_PERM ? psy : nullptr);
+        SOT_PH(sacc, 9);   // wave totals, CDF values to LDS, next row's loads issued, barrier
+
+        // ---- P4: merge of the two CDFs (losses.py:295-313), E steps per thread
+        float acc = 0.0f;
+        __builtin_amdgcn_s_setprio(kWalkPrio);
+        // (Thread t merges segment t.  Permuting the segments over the lanes -- segment 19 t mod G etc., to change the LDS bank
+        // pattern of the walk -- was measured 1.5-6 % slower for ten multipliers; E = 16 instead of 17 is 13 % slower.)
+        if (GA == G || t < GA) {
+            constexpr int VOFF = L.nU - L.padcap + PAD;  // V - Uw in floats
+            const int D0 = t * E;
+            (void)VOFF;
+            const uint32_t ub1 = lds_addr(Uw) - 4u;                        // address of Uw[-1]
+            const uint32_t vd1 = lds_addr(V) + 4u * (uint32_t)D0 + ub1;    // address of V[D0], + ub1
+            const uint32_t pb = merge_path_fixed32<N + PAD, N>(ub1, vd1, D0);  // address of Uw[i0 - 1]
+            SOT_PH(sacc, 10);  // partition search
+            const uint32_t ou = pb + 4u;     // address of Uw[i0]
+            const uint32_t ov = vd1 - pb;    // address of V[D0 - i0]
+            constexpr uint32_t ROWB = 4u * (uint32_t)L.rowf;  // the positions lie (ROWS - rg) row regions behind this row
+            if (ROWS == 1 || rg == ROWS - 1) acc = merge_walk_full<E, PM, LIM, ROWB>(ou, ov, D0 == 0, a.p);
+            else if (ROWS == 2 || rg == ROWS - 2) acc = merge_walk_full<E, PM, LIM, 2u * ROWB>(ou, ov, D0 == 0, a.p);
+            else if (ROWS == 3 || rg == ROWS - 3) acc = merge_walk_full<E, PM, LIM, 3u * ROWB>(ou, ov, D0 == 0, a.p);
+            else acc = merge_walk_full<E, PM, LIM, 4u * ROWB>(ou, ov, D0 == 0, a.p);
+        }
+        __builtin_amdgcn_s_setprio(0);
+        SOT_PH(sacc, 11);  // merge walk
+        acc = wave_sum(acc);
+        if (NW == 1) {
+            if (lane == 0 && valid && a.row_loss) store_row_loss(a.row_loss, row, acc, a.mt.counters != nullptr);
+            row_sync<NW>();  // this row's LDS reads are done before the next row's staging
+        } else {
+            if (lane == 0) red[wv] = acc;
+            row_sync<NW>();
+            if (t == 0 && valid && a.row_loss) {
+                float tot = red[0];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) tot += red[w];
+                store_row_loss(a.row_loss, row, tot, a.mt.counters != nullptr);
+            }
+        }
+        SOT_PH(sacc, 12);  // wave sum, barrier, store
+#ifdef SOT_STAMPS
+        if (sacc != nullptr) sacc[0] += 1;
+#endif
+    }
+#ifdef SOT_STAMPS
+    if (sacc != nullptr) { for (int i = 0; i < 16; ++i) g_stamps[i] = sacc[i]; }
+#endif
+    if (a.mt.counters != nullptr) batch_mean_tail<ROWS * G>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Merge-free forward for p = 1 when both measures live on ONE sorted grid (SOT_FLAG_SAME_GRID; every reference call site:
+// y_pos = x_pos.clone() in trainer.py:191, the fixed_x buffer of metrics.py:148), no quantile cutoff.
+//
+// For p = 1 the loss  sum_k (Q_k - Q_{k-1}) |uq_k - vq_k|  (losses.py:301-313) is the area between the two inverse CDFs
+// q -> xs[min(#{U < q}, n-1)] and q -> ys[min(#{V < q}, m-1)] over q in (0, max(U_last, V_last)].  Read along the position
+// axis instead of the level axis, the same area is  integral |U~(s) - V~(s)| ds  with U~(s) = U_i on [xs_i, xs_{i+1}) and
+// U~ = V~ = max(U_last, V_last) from the last support point on (the clamp of losses.py:220 maps every level beyond a
+// measure's total mass to its last point).  On a common grid both step functions jump at the same places, hence
+//        loss = sum_{i < n-1} |U_i - V_i| (xs_{i+1} - xs_i):
+// no sort of cat(U, V), no searchsorted, no gather -- the CDF values never leave the registers of the thread that
+// scanned them.  Same fp32 U, V as the merge kernel (shared CDF builder); the two closed forms differ only in the rounding
+// of 2047 non-negative products and their sum (observed <= 3e-7 relative; tests pin it to the reference at 1e-5).
+// The row pipeline shrinks to staging, ATen-ordered masses, division, fp64 scans and one fused multiply-add per element:
+// 5 barriers per row instead of 8, 18 KB of LDS per 2048-bin row instead of 34.5 KB.
+// ---------------------------------------------------------------------------------------------
+constexpr int kAreaMinWaves = 1;
+template <int G, int CPT, int ROWS, bool SQ, int NX = 0>
+__global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWaves) void sot_area_full_kernel(const FwdArgs a)
+{
+    using Geo = FullGeo<G, CPT, ROWS, false, NX>;
+    constexpr FullLayout L = Geo::L;
+    constexpr int N = Geo::N, NW = Geo::NW;
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // ROWS row regions; no position copy
+    const int64_t row_step = (int64_t)gridDim.x * ROWS;
+    int64_t row0 = (int64_t)blockIdx.x * ROWS;
+    const int tid = threadIdx.x;
+    FullCtx c;
+    c.rg = __builtin_amdgcn_readfirstlane(tid / G);
+    c.t = tid - c.rg * G;
+    c.lane = tid & (kWave - 1);
+    c.wv = __builtin_amdgcn_readfirstlane(c.t >> 6);
+    const int rg = c.rg, t = c.t, lane = c.lane, wv = c.wv;
+    float rx[CPT], ry[CPT];
+    if (row0 < a.B) {
+        const int64_t r = min(row0 + rg, a.B - 1);
+        fetch_row<G, CPT, NX>(a.x + r * a.xs, a.y + r * a.ys, t, a.n, rx, ry);
+    }
+    c.dn = a.flags & SOT_FLAG_DONT_NORMALIZE;
+    float* const base = smem + rg * L.rowf;
+    c.U = base + L.padcap; c.V = base + L.nU; c.part = base + L.part; c.colbuf = base + L.colbuf;
+    c.wtot = reinterpret_cast<double*>(base + L.wtot);
+    c.red = base + L.red; c.Sv = c.red + NW;
+    c.Uw = c.U; c.PX = nullptr; c.PY = nullptr;
+    c.x_ident = true; c.y_ident = true;
+    if (a.ident != nullptr) { c.x_ident = a.ident[0] != 0; c.y_ident = a.ident[1] != 0; }
+    // widths of the grid cells behind the CPT elements this thread owns (sorted order); 0 behind the last point.  (Kept in
+    // registers: a table in LDS read per row -- 97 -> 96 VGPRs, 5 waves per SIMD -- measured 31.0 instead of 30.3 us.)
+    float dx[CPT];
+    {
+        const int e0 = t * CPT;
+        float pe[CPT + 1];
+        const int nreal = Geo::RT ? a.n : N;   // points past a run-time-length row sit at its last position: cells of width 0
+#pragma unroll
+        for (int k = 0; k <= CPT; ++k) pe[k] = a.xpos[min(e0 + k, nreal - 1)];
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) dx[k] = (e0 + k + 1 < nreal) ? pe[k + 1] - pe[k] : 0.0f;
+    }
+    float* const red = c.red;
+#ifdef SOT_STAMPS
+    unsigned long long sbuf[16] = {};
+    unsigned long long* const sacc = (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2) ? sbuf : nullptr;
+#endif
+
+    for (; row0 < a.B; row0 += row_step) {
+        const int64_t row = row0 + rg;
+        const bool valid = row < a.B;
+        const bool more = row0 + row_step < a.B;
+        const int64_t rn = min(row0 + row_step + rg, a.B - 1);
+        float wx[CPT], wy[CPT], cu[CPT], cv[CPT];
+        float Sx, Sy;
+#ifdef SOT_STAMPS
+        if (sacc != nullptr) sacc[15] = __builtin_readcyclecounter();
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
+                                                            more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc);
+        SOT_PH(sacc, 9);   // wave totals, CDF values, next row's loads issued
+#else
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
+                                                            more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv);
+#endif
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) acc = fmaf(fabsf(cu[k] - cv[k]), dx[k], acc);
+        acc = wave_sum(acc);
+        if (NW == 1) {
+            if (lane == 0 && valid && a.row_loss) store_row_loss(a.row_loss, row, acc, a.mt.counters != nullptr);
+            row_sync<NW>();  // red / Sv of this row are consumed before the next row rewrites them
+        } else {
+            if (lane == 0) red[wv] = acc;
+            row_sync<NW>();
+            if (t == 0 && valid && a.row_loss) {
+                float tot = red[0];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) tot += red[w];
+                store_row_loss(a.row_loss, row, tot, a.mt.counters != nullptr);
+            }
+        }
+#ifdef SOT_STAMPS
+        SOT_PH(sacc, 10);  // area, wave sum, barrier 5, store
+        if (sacc != nullptr) sacc[0] += 1;
+#endif
+    }
+#ifdef SOT_STAMPS
+    if (sacc != nullptr) { for (int i = 0; i < 16; ++i) g_stamps[i] = sacc[i]; }
+#endif
+    if (a.mt.counters != nullptr) batch_mean_tail<ROWS * G>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Merge-free p = 1 kernel for SHORT rows, TWO rows per wavefront (round 3).  A 257-bin row on 64 lanes x 5 elements leaves a fifth of
+// the wave idle and pays every per-row fixed cost (scans, reductions, the mass fold, the store) for 257 points; here a row is
+// owned by HALF a wave -- 32 lanes x CPT elements (9 for 257 bins, 5 for 129) -- so one instruction stream serves two rows.  The scans
+// stop at the half-wave (the DPP row_bcast:31 step is left out), row state that the one-wave kernels keep in scalar registers is per
+// lane, and ATen's 32 summation columns are exactly the 32 lanes: a column's sum comes from the registers the lane fetched (elements
+// l, l + 32, ...), only the eight-way fold goes through LDS.  No workgroup barrier; arithmetic and its order per row are those of
+// sot_area_full_kernel (the thread-local grouping of the sums differs: equal to ~1e-7, not bit for bit).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double half_incl_scan(double v)   // inclusive scan over each 32-lane half
+{
+    v += dpp_f64_shr<kRowShr1>(v);
+    v += dpp_f64_shr<kRowShr2>(v);
+    v += dpp_f64_shr<kRowShr4>(v);
+    v += dpp_f64_shr<kRowShr8>(v);
+    v += dpp_f64<kRowBcast15, 0xA>(v);
+    return v;
+}
+__device__ __forceinline__ double half_shift_right1(double v, int l)   // lanes 0 and 32 get 0
+{
+    const double s = dpp_f64<kWaveShr1>(v);
+    return l == 0 ? 0.0 : s;
+}
+__device__ __forceinline__ float half_sum(float v, int h)   // each half's total in all of its lanes
+{
+    v += dpp_f32<kRowShr1>(v);
+    v += dpp_f32<kRowShr2>(v);
+    v += dpp_f32<kRowShr4>(v);
+    v += dpp_f32<kRowShr8>(v);
+    v += dpp_f32<kRowBcast15, 0xA>(v);
+    const float t0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
+    const float t1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+    return h ? t1 : t0;
+}
+
+// one half-wave row: element l + 32 k of the row at x / y
+template <int CPT, int N>
+__device__ __forceinline__ void half_fetch(const float* __restrict__ x, const float* __restrict__ y, int l, float (&rx)[CPT], float (&ry)[CPT])
+{
+    constexpr int NK = (N + 31) >> 5;
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+        rx[k] = 0.0f; ry[k] = 0.0f;
+        if (k < NK) {
+            const int e = l + 32 * k;
+            if ((k + 1) * 32 <= N || e < N) { rx[k] = x[e]; ry[k] = y[e]; }
+        }
+    }
+}
+
+// staging (original column order) and ATen's column sums: column l = elements l, l + 32, ... in that order, straight from the registers
+template <int CPT, bool SQ, int N>
+__device__ __forceinline__ void half_stage(float* U, float* V, float* colbuf, int l, const float (&rx)[CPT], const float (&ry)[CPT])
+{
+    constexpr int NSTEPS = N >> 5, NK = (N + 31) >> 5;
+    float ax = 0.0f, ay = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int e = l + 32 * k;
+        if ((k + 1) * 32 <= N || e < N) { U[e] = rx[k]; V[e] = ry[k]; }
+        if (k < NSTEPS) { ax += SQ ? rx[k] * rx[k] : rx[k]; ay += SQ ? ry[k] * ry[k] : ry[k]; }
+    }
+    colbuf[l] = ax; colbuf[32 + l] = ay;
+}
+
+// row masses (the eight-way fold of ATen's columns + its scalar tail), the owned elements in sorted order, safe_divide and the
+// fp64-accumulated CDFs of full_build_cdfs (P2 / P3) for a half-wave row: cu / cv = CDF values of the CPT owned elements
+template <int CPT, bool SQ, int N>
+__device__ __forceinline__ void half_cdfs(const FwdArgs& a, const float* U, const float* V, const float* colbuf, int l, bool dn, bool x_ident,
+                                          bool y_ident, float (&cu)[CPT], float (&cv)[CPT])
+{
+    const int e0 = l * CPT;
+    const float Sx = mass_fold_nx<SQ, N, false>(U, colbuf);
+    const float Sy = dn ? Sx : mass_fold_nx<SQ, N, false>(V, colbuf + 32);
+    float wx[CPT], wy[CPT];
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+        const bool in = e0 + k < N;
+        const int sx = in ? (x_ident ? e0 + k : a.xperm[e0 + k]) : 0;
+        const int sy = in ? (y_ident ? e0 + k : a.yperm[e0 + k]) : 0;
+        wx[k] = in ? U[sx] : 0.0f;
+        wy[k] = in ? V[sy] : 0.0f;
+    }
+    const float Sxh = guard_mass(Sx), Syh = guard_mass(Sy);
+    const float rSx = 1.0f / Sxh, rSy = 1.0f / Syh;
+    double px[CPT], py[CPT];
+    double runx = 0.0, runy = 0.0;
+    {
+        float qx[CPT], qy[CPT];
+        uint32_t risk = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            qx[k] = div_by_row_constant(SQ ? wx[k] * wx[k] : wx[k], Sxh, rSx, risk);
+            qy[k] = div_by_row_constant(SQ ? wy[k] * wy[k] : wy[k], Syh, rSy, risk);
+        }
+        const bool slow = (risk < kFastDivMinBits) || !(Sxh <= 0x1p40f) || !(Syh <= 0x1p40f);
+        if (__builtin_amdgcn_ballot_w64(slow) != 0ull) {  // rare; exact either way, so the two rows of a wave may share the decision
+#pragma unroll
+            for (int k = 0; k < CPT; ++k) {
+                qx[k] = (SQ ? wx[k] * wx[k] : wx[k]) / Sxh;
+                qy[k] = (SQ ? wy[k] * wy[k] : wy[k]) / Syh;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            runx += (double)qx[k]; runy += (double)qy[k];
+            px[k] = runx; py[k] = runy;
+        }
+    }
+    const double exx = half_shift_right1(half_incl_scan(runx), l), exy = half_shift_right1(half_incl_scan(runy), l);
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) { cu[k] = (float)(exx + px[k]); cv[k] = (float)(exy + py[k]); }
+}
+
+template <int CPT, int ROWS, bool SQ, int N>
+__global__ __launch_bounds__(ROWS * 32) void sot_area_half_kernel(const FwdArgs a)
+{
+    constexpr int CAP = 32 * CPT, NSTEPS = N >> 5, NK = (N + 31) >> 5;
+    static_assert(ROWS % 2 == 0 && NK <= CPT && N <= CAP && NSTEPS >= 1 && NSTEPS < 16, "two half-wave rows per wave; one partial ATen chunk per column");
+    static_assert((N >> 3) == NSTEPS * 4, "no left-over 8-lane vectors (N mod 32 < 8)");
+    constexpr int ROWF = 2 * (CAP + 4) + 64 + 8;   // floats per row region: raw x, raw y, 2 x 32 column sums
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), l = lane & 31, h = lane >> 5, rs = tid >> 5;
+    float* const U = smem + rs * ROWF;
+    float* const V = U + CAP + 4;
+    float* const colbuf = V + CAP + 4;
+    const bool dn = a.flags & SOT_FLAG_DONT_NORMALIZE;
+    bool x_ident = true, y_ident = true;
+    if (a.ident != nullptr) { x_ident = a.ident[0] != 0; y_ident = a.ident[1] != 0; }
+    const int64_t row_step = (int64_t)gridDim.x * ROWS;
+    int64_t row0 = (int64_t)blockIdx.x * ROWS;
+    const int e0 = l * CPT;
+    float dx[CPT];   // widths of the grid cells behind the owned elements (sorted order); 0 behind the last point
+    {
+        float pe[CPT + 1];
+#pragma unroll
+        for (int k = 0; k <= CPT; ++k) pe[k] = a.xpos[min(e0 + k, N - 1)];
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) dx[k] = (e0 + k + 1 < N) ? pe[k + 1] - pe[k] : 0.0f;
+    }
+    float rx[CPT], ry[CPT];
+    if (row0 < a.B) { const int64_t r = min(row0 + rs, a.B - 1); half_fetch<CPT, N>(a.x + r * a.xs, a.y + r * a.ys, l, rx, ry); }
+
+    for (; row0 < a.B; row0 += row_step) {
+        const int64_t row = row0 + rs;
+        const bool valid = row < a.B;
+        half_stage<CPT, SQ, N>(U, V, colbuf, l, rx, ry);
+        if (row0 + row_step < a.B) { const int64_t r = min(row0 + row_step + rs, a.B - 1); half_fetch<CPT, N>(a.x + r * a.xs, a.y + r * a.ys, l, rx, ry); }
+        row_sync<1>();
+        float cu[CPT], cv[CPT];
+        half_cdfs<CPT, SQ, N>(a, U, V, colbuf, l, dn, x_ident, y_ident, cu, cv);
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) acc = fmaf(fabsf(cu[k] - cv[k]), dx[k], acc);
+        acc = half_sum(acc, h);
+        if (l == 0 && valid && a.row_loss) store_row_loss(a.row_loss, row, acc, a.mt.counters != nullptr);
+        row_sync<1>();   // this row's LDS reads are done before the next row is staged
+    }
+    if (a.mt.counters != nullptr) batch_mean_tail<ROWS * 32>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
+}
+
+// The merge forward (sot_forward_full_kernel) in the same form: two rows per wave, each with its own copy of the positions behind its
+// levels (the walk finds the position of the level at LDS address o at o + POFF4), 32 merge segments of E levels per row.
+template <int CPT, int ROWS, int PM, bool LIM, bool SQ, int N>
+struct HalfRowGeo {
+    static constexpr int CAP = 32 * CPT, K = 2 * N, E = merge_steps(K, 32), GA = (K + E - 1) / E, PAD = GA * E - K;
+    static constexpr int PADCAP = align4(E) + 4, NU = PADCAP + CAP + 4, NV = CAP + 4;
+    static constexpr int POFF = NU + NV + 64;              // levels [pad | U | V], 2 x 32 column sums, then positions [pad | PX | PY]
+    static constexpr int ROWF = POFF + NU + NV;
+    static_assert(GA <= 32 && PAD + 1 <= PADCAP, "every lane walks at most one segment; room for the virtual predecessor");
+};
+
+template <int CPT, int ROWS, int PM, bool LIM, bool SQ, int N>
+__global__ __launch_bounds__(ROWS * 32) void sot_forward_half_kernel(const FwdArgs a)
+{
+    using H = HalfRowGeo<CPT, ROWS, PM, LIM, SQ, N>;
+    constexpr int CAP = H::CAP, NSTEPS = N >> 5, NK = (N + 31) >> 5, E = H::E, GA = H::GA, PAD = H::PAD;
+    static_assert(ROWS % 2 == 0 && NK <= CPT && N <= CAP && NSTEPS >= 1 && NSTEPS < 16 && (N >> 3) == NSTEPS * 4, "see sot_area_half_kernel");
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), l = lane & 31, h = lane >> 5, rs = tid >> 5;
+    float* const base = smem + rs * H::ROWF;
+    float* const U = base + H::PADCAP;
+    float* const V = base + H::NU;
+    float* const colbuf = base + H::NU + H::NV;
+    float* const PX = U + H::POFF;
+    float* const PY = V + H::POFF;
+    const bool dn = a.flags & SOT_FLAG_DONT_NORMALIZE;
+    bool x_ident = true, y_ident = true;
+    if (a.ident != nullptr) { x_ident = a.ident[0] != 0; y_ident = a.ident[1] != 0; }
+    // once: this row region's copy of the sorted positions, front padding, sentinels, virtual predecessors (full_setup)
+    for (int e = l; e < N; e += 32) { PX[e] = a.xpos[e]; PY[e] = a.ypos[e]; }
+    if (l < PAD) { PX[l - PAD] = a.xpos[0]; U[l - PAD] = 0.0f; }
+    if (l == 0) {
+        PX[N] = a.xpos[N - 1]; PY[N] = a.ypos[N - 1];      // clamp of losses.py:220
+        U[N] = INFINITY; V[N] = INFINITY;                    // an exhausted side never wins the merge
+        U[-PAD - 1] = -INFINITY; V[-1] = -INFINITY;          // never win the fmaxf that rebuilds Q_{k-1}
+    }
+    const int64_t row_step = (int64_t)gridDim.x * ROWS;
+    int64_t row0 = (int64_t)blockIdx.x * ROWS;
+    const int e0 = l * CPT;
+    float rx[CPT], ry[CPT];
+    if (row0 < a.B) { const int64_t r = min(row0 + rs, a.B - 1); half_fetch<CPT, N>(a.x + r * a.xs, a.y + r * a.ys, l, rx, ry); }
+    row_sync<1>();
+
+    for (; row0 < a.B; row0 += row_step) {
+        const int64_t row = row0 + rs;
+        const bool valid = row < a.B;
+        half_stage<CPT, SQ, N>(U, V, colbuf, l, rx, ry);
+        row_sync<1>();
+        float cu[CPT], cv[CPT];
+        half_cdfs<CPT, SQ, N>(a, U, V, colbuf, l, dn, x_ident, y_ident, cu, cv);
+        row_sync<1>();   // every lane has read its raw weights: the levels may replace them
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            if (e0 + k < N) { U[e0 + k] = cu[k]; V[e0 + k] = cv[k]; }
+        }
+        if (row0 + row_step < a.B) { const int64_t r = min(row0 + row_step + rs, a.B - 1); half_fetch<CPT, N>(a.x + r * a.xs, a.y + r * a.ys, l, rx, ry); }
+        row_sync<1>();
+        float acc = 0.0f;
+        if (GA == 32 || l < GA) {
+            const int D0 = l * E;
+            const uint32_t ub1 = lds_addr(U - PAD) - 4u;                  // address of Uw[-1]
+            const uint32_t vd1 = lds_addr(V) + 4u * (uint32_t)D0 + ub1;   // address of V[D0], + ub1
+            const uint32_t pb = merge_path_fixed32<N + PAD, N>(ub1, vd1, D0);
+            acc = merge_walk_full<E, PM, LIM, 4u * (uint32_t)H::POFF>(pb + 4u, vd1 - pb, D0 == 0, a.p);
+        }
+        acc = half_sum(acc, h);
+        if (l == 0 && valid && a.row_loss) store_row_loss(a.row_loss, row, acc, a.mt.counters != nullptr);
+        row_sync<1>();   // this row's LDS reads are done before the next row is staged
+    }
+    if (a.mt.counters != nullptr) batch_mean_tail<ROWS * 32>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
+}
+
+template <int G, int CPT, int ROWS, bool SQ, int NX>
+static hipError_t launch_area_full(const FwdArgs& a, hipStream_t s)
+{
+    constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
+    return launch_persistent<sot_area_full_kernel<G, CPT, ROWS, SQ, NX>, true>(a, sizeof(float) * (size_t)ROWS * (size_t)L.rowf, (a.B + ROWS - 1) / ROWS,
+                                                                               ROWS * G, s);
+}
+
+template <int G, int CPT, int ROWS, int NX = 0>
+static hipError_t dispatch_area_full_g(const FwdArgs& a, hipStream_t s)
+{
+    return (a.flags & SOT_FLAG_SQUARE) ? launch_area_full<G, CPT, ROWS, true, NX>(a, s) : launch_area_full<G, CPT, ROWS, false, NX>(a, s);
+}
+
+template <int CPT, int ROWS, bool SQ, int N>
+static hipError_t launch_area_half(const FwdArgs& a, hipStream_t s)
+{
+    constexpr size_t lds = sizeof(float) * (size_t)ROWS * (2 * (32 * CPT + 4) + 64 + 8);
+    return launch_persistent<sot_area_half_kernel<CPT, ROWS, SQ, N>, true>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * 32, s);
+}
+
+template <int CPT, int ROWS, int N>
+static hipError_t dispatch_area_half(const FwdArgs& a, hipStream_t s)
+{
+    return (a.flags & SOT_FLAG_SQUARE) ? launch_area_half<CPT, ROWS, true, N>(a, s) : launch_area_half<CPT, ROWS, false, N>(a, s);
+}
+
+template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool RP = false>
+static hipError_t launch_forward_full(const FwdArgs& a, hipStream_t s)
+{
+    constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
+    return launch_persistent<sot_forward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, RP>, true>(a, sizeof(float) * (size_t)L.total, (a.B + ROWS - 1) / ROWS,
+                                                                                               ROWS * G, s);
+}
+
+template <int G, int CPT, int ROWS, int NX = 0>
+static hipError_t dispatch_forward_full_g(int pm, const FwdArgs& a, hipStream_t s)
+{
+    static_assert(sizeof(float) * (size_t)full_layout<G, CPT, ROWS, false, NX>().total <= kLdsLimit, "workgroup fits one CU's LDS");
+    return with_mode(pm, a.flags, [&](auto md) { using M = decltype(md); return launch_forward_full<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX>(a, s); });
+}
+
+// Per-row positions with handed-over permutations on the compile-time geometries of 2048- / 1024- / 512-point rows, ONE row per workgroup (round 6).
+// Preconditions (run_forward): n == m in {512, 1024, 2048}, rows and permutation rows 16-byte aligned, a.perm_in complete, SOT_FLAG_REQUIRE_SORT.
+template <int G>
+static hipError_t dispatch_forward_full_rowpos_g(int pm, const FwdArgs& a, hipStream_t s)
+{
+    return with_mode(pm, a.flags, [&](auto md) { using M = decltype(md); return launch_forward_full<G, 8, 1, M::PM, M::LIM, M::SQ, 0, true>(a, s); });
+}
+
+template <int CPT, int ROWS, int PM, bool LIM, bool SQ, int N>
+static hipError_t launch_forward_half(const FwdArgs& a, hipStream_t s)
+{
+    constexpr size_t lds = sizeof(float) * (size_t)ROWS * HalfRowGeo<CPT, ROWS, PM, LIM, SQ, N>::ROWF;
+    return launch_persistent<sot_forward_half_kernel<CPT, ROWS, PM, LIM, SQ, N>, true>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * 32, s);
+}
+
+template <int CPT, int ROWS, int N>
+static hipError_t dispatch_forward_half(int pm, const FwdArgs& a, hipStream_t s)
+{
+    return with_mode(pm, a.flags, [&](auto md) { using M = decltype(md); return launch_forward_half<CPT, ROWS, M::PM, M::LIM, M::SQ, N>(a, s); });
+}
+
+}  // namespace sot

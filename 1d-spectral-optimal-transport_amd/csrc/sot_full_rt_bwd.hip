@@ -1,6 +1,6 @@
 // sot_full_rt_bwd.hip -- full-row backward kernels for run-time row lengths (full_rt_capacity);
-// the kernel and launch templates are in sot_forward_full.inc.
-#include "sot_forward_full.inc"
+// the kernel and launch templates are in sot_full_bwd.hpp.
+#include "sot_full_bwd.hpp"
 
 namespace sot {
 

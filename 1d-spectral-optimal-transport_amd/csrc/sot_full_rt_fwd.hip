@@ -1,6 +1,6 @@
 // sot_full_rt_fwd.hip -- full-row forward kernels for run-time row lengths (full_rt_capacity);
-// the kernel and launch templates are in sot_forward_full.inc.
-#include "sot_forward_full.inc"
+// the kernel and launch templates are in sot_full_fwd.hpp.
+#include "sot_full_fwd.hpp"
 
 namespace sot {
 

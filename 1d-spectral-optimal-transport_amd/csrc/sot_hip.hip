@@ -1,6 +1,6 @@
 // sot_hip.hip -- MI355X (gfx950) C ABI of the 1-D spectral optimal-transport loss: the small kernels (position plan, batch mean,
 // sorts), launch setup, the routing of a call to its row kernel (run_forward / run_backward) and the extern "C" entry points.
-// The row kernels are in sot_rows.hpp (generic) and sot_forward_full.inc (compile-time geometries); build.py lists the objects.
+// The row kernels are in sot_rows.hpp (generic) and sot_full_fwd.hpp / sot_full_bwd.hpp (compile-time geometries); build.py lists the objects.
 #include "sot_launch.hpp"
 
 namespace sot {
@@ -503,14 +503,14 @@ int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, fl
     const bool full_rt = !full && !l.rowpos && !quant && pr->n == pr->m && full_rt_capacity(pr->n) != 0 &&
                    !(pr->flags & (SOT_FLAG_PRENORMALIZED | SOT_FLAG_NO_SPECIALIZE));
     // per-row positions with their permutations at hand (handed in, or just written by the pre-sort kernel), 2048- / 1024- / 512-point rows: the
-    // compile-time-length kernel with a position copy of its own per row (sot_forward_full.inc: RP)
+    // compile-time-length kernel with a position copy of its own per row (sot_full_fwd.hpp: RP)
     const bool full_rp = l.rowpos && l.a.perm_in != nullptr && !quant && (pr->n == 2048 || pr->n == 1024 || pr->n == 512) && pr->m == pr->n && l.vec && (pr->flags & SOT_FLAG_REQUIRE_SORT) &&
                    (reinterpret_cast<uintptr_t>(l.a.perm_in) & 15) == 0 && !(pr->flags & (SOT_FLAG_PRENORMALIZED | SOT_FLAG_NO_SPECIALIZE));
     if (full_rp) return dispatch_forward_full_rowpos(l.pm, l.a, l.s) == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
-    // p = 1 on one grid shared by both measures, no cutoff: the merge-free kernel (sot_forward_full.inc: sot_area_full_kernel)
+    // p = 1 on one grid shared by both measures, no cutoff: the merge-free kernel (sot_full_fwd.hpp: sot_area_full_kernel)
     const bool area = (full || full_rt) && l.pm == 1 && (pr->flags & SOT_FLAG_SAME_GRID) && !(pr->flags & (SOT_FLAG_LIMIT_Q | SOT_FLAG_NO_AREA));
     const hipError_t e = area       ? (full ? dispatch_area_full(l.a, l.s) : dispatch_area_full_rt(l.a, l.s))
-                         : full     ? dispatch_forward_full(l.cfg, l.pm, l.a, l.lds, l.want, l.block, l.s)
+                         : full     ? dispatch_forward_full(l.pm, l.a, l.s)
                          : full_rt  ? dispatch_forward_full_rt(l.pm, l.a, l.s)
                          : l.rowpos ? dispatch_forward<true>(l.cfg, quant, l.pm, l.vec, l.a, l.lds, l.want, l.block, l.s)
                                     : dispatch_forward<false>(l.cfg, quant, l.pm, l.vec, l.a, l.lds, l.want, l.block, l.s);
@@ -545,14 +545,14 @@ int run_backward(const sot_problem* pr, const float* grad_row, int64_t grad_row_
         if (mean_tail != nullptr) b.f.mt = *mean_tail;
         if (fused) *fused = true;
     }
-    // p = 1 on one grid, gradient w.r.t. y alone, no cutoff: the merge-free training form (sot_forward_full.inc: sot_area_train_kernel)
+    // p = 1 on one grid, gradient w.r.t. y alone, no cutoff: the merge-free training form (sot_full_bwd.hpp: sot_area_train_kernel)
     // -- OPT-IN (SOT_FLAG_TIE_FREE_GRADIENT): at exactly tied levels it returns the derivative in the CDF values, not the reference's
     // float32 tie-order artefact
     const bool area = full && gx == nullptr && l.pm == 1 && area_train_supports(pr->n) && (pr->flags & SOT_FLAG_SAME_GRID) && (pr->flags & SOT_FLAG_TIE_FREE_GRADIENT) &&
                       !(pr->flags & (SOT_FLAG_LIMIT_Q | SOT_FLAG_NO_AREA));
     const hipError_t e = area       ? dispatch_area_train(b, l.s)
                          : full_rp  ? dispatch_backward_full_rowpos(l.pm, b, l.s)
-                         : full     ? dispatch_backward_full(l.cfg, l.pm, b, l.s)
+                         : full     ? dispatch_backward_full(l.pm, b, l.s)
                          : full_rt  ? dispatch_backward_full_rt(l.pm, b, l.s)
                          : l.rowpos ? dispatch_backward<true>(l.cfg, l.pm, l.vec, b, l.lds, l.want, l.block, l.s)
                                     : dispatch_backward<false>(l.cfg, l.pm, l.vec, b, l.lds, l.want, l.block, l.s);

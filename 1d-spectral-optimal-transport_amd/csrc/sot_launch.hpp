@@ -1,5 +1,6 @@
 // sot_launch.hpp -- host side shared by the row-kernel objects: launch configuration (pick_cfg), resident-grid caches, argument
-// validation, workspace layout, kernel-attached timing, and the declarations of what one object calls in another.
+// validation, workspace layout, kernel-attached timing, the launch of a persistent kernel (launch_persistent), the switch from the
+// run-time cost / cutoff / square_dist mode to template arguments (with_mode), and the declarations of what one object calls in another.
 #pragma once
 #include "sot_rows.hpp"
 
@@ -81,7 +82,7 @@ static inline int resident_grid(Kernel kern, int block, size_t lds, int64_t want
 
 // resident_grid() of one kernel instantiation, cached per device (and per LDS size: the generic kernels' LDS request
 // depends on n, m); the first use on a device also opts the kernel in to the CU's full LDS THERE (hipFuncSetAttribute
-// applies to the current device only).  One cache per call site: `Tag` is the kernel's own function-pointer type.
+// applies to the current device only).  One cache per kernel: launch_persistent below owns it.
 struct GridCache {
     std::mutex mu;
     struct Entry { size_t lds; int grid; bool attr; } e[kMaxDevices] = {};
@@ -163,6 +164,52 @@ static inline void launch_maybe_profiled(Kernel kern, int grid, int block, size_
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, a);
 }
 
+// The launch of a persistent kernel: its grid of resident workgroups from a cache of its own (one per kernel `Kern`, per device inside;
+// function-local static: thread-safe initialisation), never more workgroups than the `want` row groups, and the launch's own error.
+// PROFILED: the launch goes through launch_maybe_profiled, i.e. it consumes an armed sot_profile_next_launch (the full-row kernels only).
+template <auto Kern, bool PROFILED = false, class Args>
+static inline hipError_t launch_persistent(const Args& args, size_t lds, int64_t want, int block, hipStream_t s)
+{
+    static GridCache cache;
+    const int grid = persistent_grid(want, cached_resident_grid(cache, Kern, block, lds));
+    (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
+    if constexpr (PROFILED) launch_maybe_profiled(Kern, grid, block, lds, s, args);
+    else hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, s, args);
+    return hipGetLastError();
+}
+
+// ---- run-time mode -> compile-time template arguments.  pm: 1 -> p == 1, 2 -> p == 2, 0 -> any other p >= 1 (powf in the walk;
+// losses.py:313 takes any p at one speed, and so do the full-row kernels: round 2 sent such calls to the generic kernel, 4x slower at
+// 8192 x 2048).  with_pm(pm, f) calls f(std::integral_constant<int, PM>{}); with_mode(pm, flags, f) calls f(Mode<PM, LIM, SQ>{}) with
+// the quantile cutoff (SOT_FLAG_LIMIT_Q) and square_dist (SOT_FLAG_SQUARE) of `flags`: f is instantiated for all 3 / all 12 modes.
+template <int PM_, bool LIM_, bool SQ_>
+struct Mode { static constexpr int PM = PM_; static constexpr bool LIM = LIM_, SQ = SQ_; };
+
+template <class F>
+static inline hipError_t with_pm(int pm, F&& f)
+{
+    switch (pm) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: return f(std::integral_constant<int, 0>{});
+    }
+}
+
+template <class F>
+static inline hipError_t with_mode(int pm, uint32_t flags, F&& f)
+{
+    const bool lim = flags & SOT_FLAG_LIMIT_Q, sq = flags & SOT_FLAG_SQUARE;
+    return with_pm(pm, [&](auto pmc) {
+        constexpr int PM = decltype(pmc)::value;
+        switch ((lim ? 2 : 0) | (sq ? 1 : 0)) {
+            case 0: return f(Mode<PM, false, false>{});
+            case 1: return f(Mode<PM, false, true>{});
+            case 2: return f(Mode<PM, true, false>{});
+            default: return f(Mode<PM, true, true>{});
+        }
+    });
+}
+
 // ---- cross-object host interface (the objects are linked into one shared library; each function names its defining file) ----
 struct Launch {
     FwdArgs a;
@@ -183,14 +230,14 @@ template <bool ROWPOS>
 hipError_t dispatch_backward(const LaunchCfg& c, int pm, bool vec, const BwdArgs& b, size_t lds, int64_t want, int block,
                              hipStream_t s);
 // sot_full_fwd.hip
-hipError_t dispatch_forward_full(const LaunchCfg& c, int pm, const FwdArgs& a, size_t lds, int64_t want, int block, hipStream_t s);
+hipError_t dispatch_forward_full(int pm, const FwdArgs& a, hipStream_t s);
 hipError_t dispatch_forward_full_rowpos(int pm, const FwdArgs& a, hipStream_t s);   // per-row positions through handed-over permutations, 2048-point rows (round 6)
 hipError_t dispatch_area_full(const FwdArgs& a, hipStream_t s);
 bool forward_full_supports(int n, bool aligned16);
 bool backward_full_supports(int n, bool aligned16);
 int full_rt_capacity(int n);   // capacity of the compile-time geometry that takes a run-time row length n (0: none)
 // sot_full_bwd.hip
-hipError_t dispatch_backward_full(const LaunchCfg& c, int pm, const BwdArgs& b, hipStream_t s);
+hipError_t dispatch_backward_full(int pm, const BwdArgs& b, hipStream_t s);
 hipError_t dispatch_backward_full_rowpos(int pm, const BwdArgs& b, hipStream_t s);   // per-row positions through handed-over permutations, 2048-point rows (round 6)
 hipError_t dispatch_area_train(const BwdArgs& b, hipStream_t s);
 bool area_train_supports(int n);

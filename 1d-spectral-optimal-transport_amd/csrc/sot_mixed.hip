@@ -481,54 +481,23 @@ static int setup_mixed(const sot_problem* pr, void* workspace, size_t workspace_
     return SOT_OK;
 }
 
-template <typename Kernel, typename Args>
-static hipError_t launch_mixed(GridCache& cache, Kernel kern, const Args& args, size_t lds, int64_t want, int block, hipStream_t s)
-{
-    const int grid = persistent_grid(want, cached_resident_grid(cache, kern, block, lds));
-    (void)hipGetLastError();   // do not inherit a stale error from earlier runtime calls
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, args);
-    return hipGetLastError();
-}
-
-template <int G, int CPT, int PM, bool LIM>
-static hipError_t launch_mixed_forward(const MixedLaunch& l)
-{
-    static GridCache cache;   // per instantiation
-    return launch_mixed(cache, sot_mixed_forward_kernel<G, CPT, PM, LIM>, l.a, l.lds_fwd, l.want, l.block, l.s);
-}
-
-template <int G, int CPT, int PM, bool LIM>
-static hipError_t launch_mixed_backward(const MixedLaunch& l, const MixedGradArgs& b)
-{
-    static GridCache cache;
-    return launch_mixed(cache, sot_mixed_backward_kernel<G, CPT, PM, LIM>, b, l.lds_grad, l.want, l.block, l.s);
-}
-
-template <int G, int CPT>
-static hipError_t launch_mixed_position_grad(const MixedLaunch& l, const MixedGradArgs& b)
-{
-    static GridCache cache;
-    // the per-thread tails live in the row's dead CDFs when they fit there (see the kernel), else behind the rows
-    const int E = merge_steps(l.a.n + l.a.m, G), Ga = (l.a.n + l.a.m + E - 1) / E;
-    return launch_mixed(cache, sot_mixed_position_grad_kernel<G, CPT>, b, (2 * Ga <= l.a.n + l.a.m) ? l.lds_grad : l.lds_pos, l.want, l.block, l.s);
-}
-
 // KIND 0: forward, 1: weight gradients, 2: position gradient
 template <int KIND, int G, int CPT>
 static hipError_t dispatch_mixed_g(const MixedLaunch& l, const MixedGradArgs& b)
 {
-    if constexpr (KIND == 2) return launch_mixed_position_grad<G, CPT>(l, b);
-    else {
-    const bool lim = l.a.flags & SOT_FLAG_LIMIT_Q;
-#define SOT_MIXED_PM(PMV)                                                                                    \
-    if constexpr (KIND == 0) return lim ? launch_mixed_forward<G, CPT, PMV, true>(l) : launch_mixed_forward<G, CPT, PMV, false>(l); \
-    else return lim ? launch_mixed_backward<G, CPT, PMV, true>(l, b) : launch_mixed_backward<G, CPT, PMV, false>(l, b);
-    switch (l.pm) {
-        case 1: { SOT_MIXED_PM(1) }
-        case 2: { SOT_MIXED_PM(2) }
-        default: { SOT_MIXED_PM(0) }
-    }
-#undef SOT_MIXED_PM
+    if constexpr (KIND == 2) {
+        // the per-thread tails live in the row's dead CDFs when they fit there (see the kernel), else behind the rows
+        const int E = merge_steps(l.a.n + l.a.m, G), Ga = (l.a.n + l.a.m + E - 1) / E;
+        return launch_persistent<sot_mixed_position_grad_kernel<G, CPT>>(b, (2 * Ga <= l.a.n + l.a.m) ? l.lds_grad : l.lds_pos, l.want, l.block, l.s);
+    } else {
+        const bool lim = l.a.flags & SOT_FLAG_LIMIT_Q;
+        const auto launch = [&](auto pmc, auto limc) {
+            constexpr int PM = decltype(pmc)::value;
+            constexpr bool LIM = decltype(limc)::value;
+            if constexpr (KIND == 0) return launch_persistent<sot_mixed_forward_kernel<G, CPT, PM, LIM>>(l.a, l.lds_fwd, l.want, l.block, l.s);
+            else return launch_persistent<sot_mixed_backward_kernel<G, CPT, PM, LIM>>(b, l.lds_grad, l.want, l.block, l.s);
+        };
+        return with_pm(l.pm, [&](auto pmc) { return lim ? launch(pmc, std::true_type{}) : launch(pmc, std::false_type{}); });
     }
 }
 

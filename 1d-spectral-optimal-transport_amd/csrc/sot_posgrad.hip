@@ -180,13 +180,7 @@ __global__ __launch_bounds__((G < 256 ? 256 : G)) void sot_position_grad_kernel(
 template <int G, int CPT, bool ROWPOS>
 static hipError_t launch_position_grad(const PosGradArgs& b, size_t lds, int64_t want, int block, hipStream_t s)
 {
-    auto kern = sot_position_grad_kernel<G, CPT, ROWPOS>;
-    static GridCache cache;
-    const int grid_cap = cached_resident_grid(cache, kern, block, lds);
-    const int grid = persistent_grid(want, grid_cap);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, b);
-    return hipGetLastError();
+    return launch_persistent<sot_position_grad_kernel<G, CPT, ROWPOS>>(b, lds, want, block, s);
 }
 
 template <bool ROWPOS>

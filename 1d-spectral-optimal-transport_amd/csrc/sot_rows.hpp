@@ -712,7 +712,7 @@ __global__ __launch_bounds__((G < 256 ? 256 : G), ((CSR && G == 64) ? kCsrMinWav
             const int voff = (int)(V - Uw);
             uint32_t iu = (uint32_t)i0;
             if (!QUANT) {
-                // "Loser" form of the two-way merge (see sot_forward_full.inc): (w, wp) is the head fetched last, (r, rp) the
+                // "Loser" form of the two-way merge (see sot_full_fwd.hpp: merge_walk_full): (w, wp) is the head fetched last, (r, rp) the
                 // head that lost the previous comparison; only the consumed head's stream is read again, so the fetched
                 // level and position become the new (w, wp) without a select.  Equal heads may be consumed in either
                 // order: the pair of heads, hence the consumed level, its width and its cost factor, is the same, and the

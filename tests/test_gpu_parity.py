@@ -1524,7 +1524,7 @@ def test_csr_backward_dyadic_cutoff_matches_the_oracle_on_every_checked_row():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# Run-time row lengths on the compile-time geometries (round 3; csrc/sot_forward_full.inc, NX = -1): every n == m <= 8192 on
+# Run-time row lengths on the compile-time geometries (round 3; csrc/sot_full_fwd.hpp and sot_full_bwd.hpp, NX = -1): every n == m <= 8192 on
 # shared positions that has no kernel of its own runs the next capacity's geometry, its tail padded with zero-weight points at
 # the row's last position.  Same results as the generic kernels (SOT_FLAG_NO_SPECIALIZE) and as the oracle.
 # ---------------------------------------------------------------------------------------------------------------------------

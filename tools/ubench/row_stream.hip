@@ -1,6 +1,6 @@
 // row_stream.hip -- how fast can the SOT kernels' ACCESS SHAPE stream from HBM?  A persistent grid of 256-thread workgroups,
 // each fetching one [x row | y row] pair of 2 x 8 KB per iteration with four 16-B loads per thread (the staging loads of
-// sot_forward_full.inc), summing them and writing 4 bytes per row -- no LDS, no other arithmetic.  Variants: loads of the next row
+// sot_full_common.hpp), summing them and writing 4 bytes per row -- no LDS, no other arithmetic.  Variants: loads of the next row
 // issued before the current one is consumed (depth 1, what the kernels do) or two rows ahead (depth 2); 4 ... 8 workgroups per CU.
 // Build: hipcc --offload-arch=gfx950 -O3 -o row_stream row_stream.hip
 #include <hip/hip_runtime.h>
