@@ -360,6 +360,17 @@ __device__ __forceinline__ FullCtx full_setup(const FwdArgs& a, float* smem)
     return c;
 }
 
+// full_build_cdfs adds up the totals of the waves in front of a wave either in a loop over them (one LDS round trip per wave) or, for rows
+// of at most this many waves, from all totals read at once under wave-uniform selects.  The second form holds 4 (NW - 1) more registers
+// while it runs: at 8 and 16 waves per row (512- and 1024-thread rows) it cost kernels their fourth wave per SIMD (126 -> 129, 125 -> 138
+// VGPRs in the backward) or put them into scratch (8192-bin forward and merge-free kernels: 60-112 bytes); up to four waves no kernel lost a
+// wave per SIMD or gained scratch.  Forward kernels (GRAD == 0) only: 1024- and 1500-bin forwards gained 0.5-0.7 us per 16384-32768 rows, but the
+// backward kernels moved both ways (both gradients at 1500 bins 200.7 -> 199.4 us, y only at 1024 bins 70.0 -> 70.4 us, where the form
+// gave the kernel a fourth wave per SIMD, 130 -> 116 VGPRs) and keep the loop.
+constexpr int kPrefixSelectMaxWaves = 4;
+
+struct NoRowHook { __device__ __forceinline__ void operator()() const {} };   // full_build_cdfs: nothing to do behind barrier 1
+
 // P1-P3 of one row: raw weights -> LDS, row masses in ATen order, safe_divide, fp64-accumulated CDFs into U / V (ends
 // with the barrier that publishes them).  rx / ry: this row's weights (coalesced float4 layout), refilled with the next
 // row's (nxt_x / nxt_y, null at the end); wx / wy: the CPT contiguous raw weights this thread owns in sorted order.
@@ -367,11 +378,16 @@ __device__ __forceinline__ FullCtx full_setup(const FwdArgs& a, float* smem)
 // nothing is written to U / V and the closing barrier is left out (the barrier behind the raw reads already orders the next
 // row's staging behind this row's last LDS read of the raw weights).
 // RAW_OUT: wx / wy must be the weights as given (a gradient needs them); otherwise square_dist rows may be staged as their squares
-template <int G, int CPT, int ROWS, int GRAD, bool SQ, int NX = 0, bool TO_LDS = true, bool RAW_OUT = (GRAD != 0)>
+// PLAIN (the fast body of sot_area_full_kernel): the caller has checked, once per launch, that both permutations are the identity and
+// that the rows are normalised; c.dn / c.x_ident / c.y_ident are then compile-time constants here and the permuted owner reads are not
+// compiled.  after_b1(): called by every thread behind barrier 1 (that body's deferred row-loss store).  PLAIN and after_b1 belong to
+// that one caller: the merge, backward and training kernels leave both at their defaults.
+template <int G, int CPT, int ROWS, int GRAD, bool SQ, int NX = 0, bool TO_LDS = true, bool RAW_OUT = (GRAD != 0), bool PLAIN = false,
+          class AfterB1 = NoRowHook>
 __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx& c, float (&rx)[CPT], float (&ry)[CPT],
                                                 const float* nxt_x, const float* nxt_y, float (&wx)[CPT], float (&wy)[CPT],
                                                 float& Sx, float& Sy, float (&cu)[CPT], float (&cv)[CPT], unsigned long long* sacc = nullptr,
-                                                const int* psx = nullptr, const int* psy = nullptr)
+                                                const int* psx = nullptr, const int* psy = nullptr, AfterB1 after_b1 = AfterB1{})
 {
     // psx / psy (forward kernels, round 4): the staged LDS indices of the thread's CPT owned elements on a PERMUTED shared grid, looked up
     // once per workgroup instead of once per row (the plan's permutation is row-invariant; the compiler cannot hoist the loads itself:
@@ -383,7 +399,7 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     float* const U = c.U; float* const V = c.V; float* const part = c.part; float* const colbuf = c.colbuf;
     double* const wtot = c.wtot; float* const Sv = c.Sv;
     const int t = c.t, lane = c.lane, wv = c.wv;
-    const bool dn = c.dn, x_ident = c.x_ident, y_ident = c.y_ident;
+    const bool dn = PLAIN ? false : c.dn, x_ident = PLAIN ? true : c.x_ident, y_ident = PLAIN ? true : c.y_ident;
     // The RAW weights are staged with the two 16-B halves of every second 32-B block swapped (float index e lives at
     // e ^ 4 when bit 5 of e is set): the owner reads below (16 B per lane at a 32-B lane stride) then touch all 32 banks
     // instead of every bank twice.  Every address involved is a per-thread constant; the CDFs are written unswizzled.
@@ -452,6 +468,7 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     SOT_PH(sacc, 1);   // staging stores issued (includes the wait for this row's loads)
     row_sync<NW>();
     SOT_PH(sacc, 2);   // barrier 1
+    after_b1();
 
     // ---- P2: row masses in ATen order (sot_device.hpp)
     const MassPlan mp = make_mass_plan(RT ? a.n : N);   // used by the run-time-length rows only
@@ -599,9 +616,22 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     SOT_PH(sacc, 7);   // division, fp64 accumulation, wave scans
     row_sync<NW>();  // raw weights are consumed, wave totals are visible
     SOT_PH(sacc, 8);   // barrier 4
-    if constexpr (NW > 1) {
+    if constexpr (NW > 1 && (NW > kPrefixSelectMaxWaves || GRAD != 0)) {   // totals of the waves in front of this one, added in wave order ((0 + w0) + w1) + ...
         double ox = 0.0, oy = 0.0;
         for (int w = 0; w < wv; ++w) { ox += wtot[w]; oy += wtot[NW + w]; }
+        exx += ox; exy += oy;
+    } else if constexpr (NW > 1) {
+        // the same sum in the same order for forward rows of up to four waves: every total is read at its fixed address in one LDS round trip and
+        // the sum is formed with wave-uniform selects -- no loop whose trip count is the wave's index
+        double tx[NW - 1], ty[NW - 1];
+#pragma unroll
+        for (int w = 0; w < NW - 1; ++w) { tx[w] = wtot[w]; ty[w] = wtot[NW + w]; }
+        double ox = 0.0, oy = 0.0;
+#pragma unroll
+        for (int w = 0; w < NW - 1; ++w) {
+            const double sx = ox + tx[w], sy = oy + ty[w];
+            ox = (w < wv) ? sx : ox; oy = (w < wv) ? sy : oy;
+        }
         exx += ox; exy += oy;
     }
 #pragma unroll
@@ -621,7 +651,9 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
         }
     }
     // the next row's loads are issued here (not in P1): their 2*CPT destination registers are then live only during the merge
-    // phases, whose register demand is small, instead of across the register-hungry division / scan (8192 x 2048: 45.6 -> 44.8 us)
+    // phases, whose register demand is small, instead of across the register-hungry division / scan (8192 x 2048: 45.6 -> 44.8 us).
+    // The merge-free kernel has no walk to hide them behind, yet issuing them right behind barrier 1 in its plain loop (no more
+    // registers: 118 either way) was slower, 33.4 against 32.2 us per headline step (profiles/f8_area_plain_loop.txt)
     if (nxt_x != nullptr) fetch_row<G, CPT, NX>(nxt_x, nxt_y, t, a.n, rx, ry);
     if constexpr (TO_LDS) row_sync<NW>();
 }

@@ -211,6 +211,91 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? kRt512MinWaves : (
 // 5 barriers per row instead of 8, 18 KB of LDS per 2048-bin row instead of 34.5 KB.
 // ---------------------------------------------------------------------------------------------
 constexpr int kAreaMinWaves = 1;
+
+// The row loop of sot_area_full_kernel for the launch every reference call site makes: both permutations the identity, normalised rows,
+// row losses wanted, no mean tail -- tested once per launch by the kernel, compile-time constants here (full_build_cdfs: PLAIN), so the
+// loop holds neither the branches on them, nor the gathers through a.xperm / a.yperm, nor the write-through store.  Same arithmetic in
+// the same order as the general body: the row losses are bit-identical (tests/test_area_fast_loop_gpu.py).
+// Rows of several waves (NW > 1) run on THREE workgroup barriers instead of four: the wave sums of row k wait in red[] until the row
+// group's last wave -- which has no part in the mass fold, the critical path between barriers 1 and 3 -- adds them up (red[0] + red[1] +
+// ..., the order of the general body) and stores the loss behind barrier 1 of row k + 1; the workgroup's last row pays one barrier of
+// its own behind the loop.  LDS hazards of one row group, row k against row k + 1 (b1 ... b4: the barriers of full_build_cdfs):
+//   region        written                                      read                                       reuse ordered by
+//   U / V (raw)   staging of row k, before b1(k)               fold tail + owner reads, b1(k) .. b3(k)    b3(k), b4(k): row k + 1 is staged behind them
+//   part          staging of row k, before b1(k)               columns (waves 0, 1), b1(k) .. b3(k)       b3(k), b4(k)
+//   colbuf        waves 0 / 1, b1(k) .. b3(k)                  the writing wave itself (wave fence)       program order of one wave
+//   Sv            lane 0 of waves 0 / 1, b1(k) .. b3(k)        everyone, b3(k) .. b4(k)                   b4(k), b1(k + 1): rewritten behind b1(k + 1)
+//   wtot          last lane of each wave, b3(k) .. b4(k)       everyone, behind b4(k)                     b1(k + 1), b3(k + 1): rewritten behind b3(k + 1)
+//   red           lane 0 of each wave, behind b4(k)            the last wave's lane 0, behind b1(k + 1)   b3(k + 1), b4(k + 1): rewritten behind b4(k + 1)
+// Every reuse has a barrier of the next row in between: nothing is double-buffered.
+//
+// Which geometries carry the second loop body: 2048-bin rows on 256 x 8 only, where it was measured to pay (33.2 -> 32.2 us per headline
+// step, 106 -> 118 VGPRs, still four waves per SIMD).  A kernel is allocated the registers of its hungrier body, and compiled into every
+// geometry the second body cost the others an occupancy step or pushed them into scratch without a measurement to show for it:
+// 8192 bins (1024 x 8) 122 -> 128 VGPRs + 152 bytes of scratch, 4096 bins (512 x 8) 111 -> 134 (one workgroup per CU instead of two),
+// 1025 bins on one wave (64 x 17) 152 -> 192 (two waves per SIMD instead of three), run-time lengths on 512 x 8 122 -> 143; one-wave rows
+// have no workgroup barrier to lose in the first place.  Those keep the single loop.
+template <int G, int CPT, int ROWS, int NX>
+constexpr bool kAreaPlainLoop = (G == 256 && CPT == 8 && ROWS == 1 && NX == 0);
+
+template <int G, int CPT, int ROWS, bool SQ, int NX>
+__device__ __forceinline__ void area_rows_plain(const FwdArgs& a, const FullCtx& c, float (&rx)[CPT], float (&ry)[CPT], const float (&dx)[CPT],
+                                                int64_t row0, int64_t row_step, unsigned long long* sacc)
+{
+    (void)sacc;
+    constexpr int NW = FullGeo<G, CPT, ROWS, false, NX>::NW;
+    const int rg = c.rg, t = c.t, lane = c.lane, wv = c.wv;
+    float* const red = c.red;
+    float* const row_loss = a.row_loss;
+    int64_t pending = -1;   // the row whose wave sums wait in red[] (wave-uniform)
+    const auto store_pending = [&] {
+        if (NW > 1 && t == G - kWave && pending >= 0) {
+            float tot = red[0];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) tot += red[w];
+            row_loss[pending] = tot;
+        }
+    };
+    if (row0 >= a.B) return;
+    for (;;) {
+        const int64_t row = row0 + rg;
+        const bool valid = ROWS == 1 || row < a.B;
+        const int64_t next0 = row0 + row_step;
+        const bool more = next0 < a.B;
+        const int64_t rn = min(next0 + rg, a.B - 1);
+        float wx[CPT], wy[CPT], cu[CPT], cv[CPT];
+        float Sx, Sy;
+#ifdef SOT_STAMPS
+        if (sacc != nullptr) sacc[15] = __builtin_readcyclecounter();
+#endif
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, false, true>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
+                                                                         more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc,
+                                                                         nullptr, nullptr, store_pending);
+        SOT_PH(sacc, 9);   // wave totals, CDF values, next row's loads issued
+        float acc = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) acc = fmaf(fabsf(cu[k] - cv[k]), dx[k], acc);
+        acc = wave_sum(acc);
+        if (NW == 1) {
+            if (lane == 0 && valid) row_loss[row] = acc;
+            row_sync<NW>();  // Sv of this row is consumed before the next row rewrites it
+        } else {
+            if (lane == 0) red[wv] = acc;
+            pending = valid ? row : -1;
+        }
+#ifdef SOT_STAMPS
+        SOT_PH(sacc, 10);  // area, wave sum (the store: behind barrier 1 of the next row)
+        if (sacc != nullptr) sacc[0] += 1;
+#endif
+        if (!more) break;
+        row0 = next0;
+    }
+    if constexpr (NW > 1) {
+        row_sync<NW>();
+        store_pending();
+    }
+}
+
 template <int G, int CPT, int ROWS, bool SQ, int NX = 0>
 __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWaves) void sot_area_full_kernel(const FwdArgs a)
 {
@@ -256,8 +341,17 @@ __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWa
 #ifdef SOT_STAMPS
     unsigned long long sbuf[16] = {};
     unsigned long long* const sacc = (threadIdx.x == 0 && blockIdx.x == gridDim.x / 2) ? sbuf : nullptr;
+#else
+    constexpr unsigned long long* sacc = nullptr;
 #endif
 
+    // one wave-uniform test per launch: the plain launch takes the loop compiled for it, every other one the general loop below
+    constexpr bool PLAIN_LOOP = kAreaPlainLoop<G, CPT, ROWS, NX>;
+    bool plain = false;
+    if constexpr (PLAIN_LOOP) plain = c.x_ident && c.y_ident && !c.dn && a.row_loss != nullptr && a.mt.counters == nullptr;
+    if (plain) {
+        if constexpr (PLAIN_LOOP) area_rows_plain<G, CPT, ROWS, SQ, NX>(a, c, rx, ry, dx, row0, row_step, sacc);
+    } else {
     for (; row0 < a.B; row0 += row_step) {
         const int64_t row = row0 + rg;
         const bool valid = row < a.B;
@@ -296,10 +390,11 @@ __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWa
         if (sacc != nullptr) sacc[0] += 1;
 #endif
     }
+    if (a.mt.counters != nullptr) batch_mean_tail<ROWS * G>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
+    }
 #ifdef SOT_STAMPS
     if (sacc != nullptr) { for (int i = 0; i < 16; ++i) g_stamps[i] = sacc[i]; }
 #endif
-    if (a.mt.counters != nullptr) batch_mean_tail<ROWS * G>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
 }
 
 // ---------------------------------------------------------------------------------------------
