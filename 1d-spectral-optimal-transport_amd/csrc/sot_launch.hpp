@@ -167,6 +167,7 @@ static inline void launch_maybe_profiled(Kernel kern, int grid, int block, size_
 // The launch of a persistent kernel: its grid of resident workgroups from a cache of its own (one per kernel `Kern`, per device inside;
 // function-local static: thread-safe initialisation), never more workgroups than the `want` row groups, and the launch's own error.
 // PROFILED: the launch goes through launch_maybe_profiled, i.e. it consumes an armed sot_profile_next_launch (the full-row kernels only).
+// A workgroup's second and later rows are tested in tests/test_row_loop_gpu.py, on batches that force them; a new row kernel adds a line to its CASES.
 template <auto Kern, bool PROFILED = false, class Args>
 static inline hipError_t launch_persistent(const Args& args, size_t lds, int64_t want, int block, hipStream_t s)
 {

@@ -18,6 +18,9 @@ meet by chance; of the 128 checked rows these are row 6 (cutoff pairs, 0) and ro
 Tolerances are those of the tests of the same routes in test_gpu_parity.py: 1e-5 relative to the oracle (forward), 1e-5 of the row's
 largest gradient entry (backward); against the generic kernel bit for bit on the compile-time routes of rows that fill their geometry
 with p in {1, 2} (test_full_row_kernel_matches_generic, test_full_row_backward_matches_generic_and_oracle), 2e-6 elsewhere.
+
+These shapes stay in a workgroup's first row: its second and later rows are tested in tests/test_row_loop_gpu.py, where a new row kernel adds a
+line to CASES.
 """
 import functools
 import itertools
