@@ -51,7 +51,7 @@ int run_forward_csr(const float* xw, const float* xp, const int64_t* xoff, int64
     else if (cfg.G == 128) e = dispatch_forward_csr_g<128, 12>(pm, lim, a, lds, want, block, s);
     else if (cfg.G == 256) e = dispatch_forward_csr_g<256, 8>(pm, lim, a, lds, want, block, s);
     else e = dispatch_forward_csr_g<1024, 8>(pm, lim, a, lds, want, block, s);
-    return e == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 }  // namespace sot

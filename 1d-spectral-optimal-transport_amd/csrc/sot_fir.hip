@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/sot_hip.h"
+#include "sot_host.hpp"
 
 namespace sot_fir {
 
@@ -200,7 +200,7 @@ inline int launch_fir(const float* x, int64_t x_stride, const float* h, int64_t 
     a.T = (int)samples; a.L = taps; a.start = start; a.reversed = reversed;
     a.tiles = (int)((samples + kTile - 1) / kTile);
     hipLaunchKernelGGL(fir_same_kernel, dim3((unsigned)(batch * a.tiles)), dim3(kThreads), 0, st, a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 }  // namespace sot_fir
@@ -259,7 +259,7 @@ int sot_fir_same_backward(const float* grad_out, const float* audio, int64_t aud
         hipLaunchKernelGGL(fir_tap_grad_partial_kernel, dim3((unsigned)(batch * a.chunks)), dim3(kThreads), 0, st, a);
         const int64_t count = batch * n_taps;
         hipLaunchKernelGGL(fir_tap_grad_finish_kernel, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, a, count);
-        if (hipGetLastError() != hipSuccess) return SOT_ERR_LAUNCH;
+        return sot::launch_status();
     }
     return SOT_OK;
 }

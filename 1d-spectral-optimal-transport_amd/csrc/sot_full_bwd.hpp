@@ -547,7 +547,7 @@ static hipError_t launch_area_train(const BwdArgs& b, hipStream_t s)
 {
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
     const size_t lds = sizeof(float) * (size_t)ROWS * (size_t)L.rowf + sizeof(double) * (size_t)ROWS * 2 * (G / kWave);
-    return launch_persistent<sot_area_train_kernel<G, CPT, ROWS, SQ, NX>, true>(b, lds, (b.f.B + ROWS - 1) / ROWS, ROWS * G, s);
+    return launch_persistent_profiled<sot_area_train_kernel<G, CPT, ROWS, SQ, NX>>(b, lds, (b.f.B + ROWS - 1) / ROWS, ROWS * G, s);
 }
 
 template <int G, int CPT, int ROWS, int NX = 0>
@@ -560,7 +560,7 @@ template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool WANT
 static hipError_t launch_backward_full_x(const BwdArgs& b, hipStream_t s)
 {
     constexpr FullLayout L = full_layout<G, CPT, ROWS, SLIM ? 2 : 1, NX>();
-    return launch_persistent<sot_backward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, WANT_X, SLIM, MINB, RP>, true>(
+    return launch_persistent_profiled<sot_backward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, WANT_X, SLIM, MINB, RP>>(
         b, sizeof(float) * (size_t)L.total, (b.f.B + ROWS - 1) / ROWS, ROWS * G, s);
 }
 

@@ -634,7 +634,7 @@ template <int G, int CPT, int ROWS, bool SQ, int NX>
 static hipError_t launch_area_full(const FwdArgs& a, hipStream_t s)
 {
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
-    return launch_persistent<sot_area_full_kernel<G, CPT, ROWS, SQ, NX>, true>(a, sizeof(float) * (size_t)ROWS * (size_t)L.rowf, (a.B + ROWS - 1) / ROWS,
+    return launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, SQ, NX>>(a, sizeof(float) * (size_t)ROWS * (size_t)L.rowf, (a.B + ROWS - 1) / ROWS,
                                                                                ROWS * G, s);
 }
 
@@ -648,7 +648,7 @@ template <int CPT, int ROWS, bool SQ, int N>
 static hipError_t launch_area_half(const FwdArgs& a, hipStream_t s)
 {
     constexpr size_t lds = sizeof(float) * (size_t)ROWS * (2 * (32 * CPT + 4) + 64 + 8);
-    return launch_persistent<sot_area_half_kernel<CPT, ROWS, SQ, N>, true>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * 32, s);
+    return launch_persistent_profiled<sot_area_half_kernel<CPT, ROWS, SQ, N>>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * 32, s);
 }
 
 template <int CPT, int ROWS, int N>
@@ -661,7 +661,7 @@ template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool RP =
 static hipError_t launch_forward_full(const FwdArgs& a, hipStream_t s)
 {
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
-    return launch_persistent<sot_forward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, RP>, true>(a, sizeof(float) * (size_t)L.total, (a.B + ROWS - 1) / ROWS,
+    return launch_persistent_profiled<sot_forward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, RP>>(a, sizeof(float) * (size_t)L.total, (a.B + ROWS - 1) / ROWS,
                                                                                                ROWS * G, s);
 }
 
@@ -684,7 +684,7 @@ template <int CPT, int ROWS, int PM, bool LIM, bool SQ, int N>
 static hipError_t launch_forward_half(const FwdArgs& a, hipStream_t s)
 {
     constexpr size_t lds = sizeof(float) * (size_t)ROWS * HalfRowGeo<CPT, ROWS, PM, LIM, SQ, N>::ROWF;
-    return launch_persistent<sot_forward_half_kernel<CPT, ROWS, PM, LIM, SQ, N>, true>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * 32, s);
+    return launch_persistent_profiled<sot_forward_half_kernel<CPT, ROWS, PM, LIM, SQ, N>>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * 32, s);
 }
 
 template <int CPT, int ROWS, int N>

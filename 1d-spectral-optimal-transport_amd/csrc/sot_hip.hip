@@ -253,19 +253,19 @@ int launch_segmented_sort_wave(const float* keys, int64_t B, int n, int64_t stri
     constexpr bool CAN_VEC = KPL % 4 == 0;
     const bool fast = CAN_VEC && n == 64 * KPL && stride % 4 == 0 && ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(out_keys) |
                                                                      reinterpret_cast<uintptr_t>(out_idx)) & 15) == 0;
-    static GridCache cache[2];
-    const void* fn = fast ? reinterpret_cast<const void*>(sot_segmented_sort_wave_kernel<KPL, CAN_VEC>)
-                          : reinterpret_cast<const void*>(sot_segmented_sort_wave_kernel<KPL, false>);
-    allow_full_lds_once(cache[fast ? 1 : 0], fn);
     int per_cu = (int)(kLdsLimit / lds);
     if (per_cu > 16 / WGW) per_cu = 16 / WGW;
     if (per_cu < 1) per_cu = 1;
-    const int64_t groups = (B + WGW - 1) / WGW, cap = (int64_t)device_cu_count() * per_cu;
-    const int grid = (int)(groups < cap ? groups : cap);
-    (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
-    if (fast) hipLaunchKernelGGL((sot_segmented_sort_wave_kernel<KPL, CAN_VEC>), dim3(grid), dim3(64 * WGW), lds, s, keys, B, n, stride, out_keys, out_idx);
-    else hipLaunchKernelGGL((sot_segmented_sort_wave_kernel<KPL, false>), dim3(grid), dim3(64 * WGW), lds, s, keys, B, n, stride, out_keys, out_idx);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    const int grid = capped_grid((B + WGW - 1) / WGW, per_cu);
+    auto go = [&](auto vec) {
+        constexpr auto kern = sot_segmented_sort_wave_kernel<KPL, decltype(vec)::value>;
+        allow_full_lds_once<kern>();
+        (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WGW), lds, s, keys, B, n, stride, out_keys, out_idx);
+    };
+    if (fast) go(std::bool_constant<CAN_VEC>{});
+    else go(std::false_type{});
+    return launch_status();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -387,25 +387,25 @@ int launch_rowpos_sort(const float* xpos, const float* ypos, int64_t B, int n, i
     const bool aligned = ((reinterpret_cast<uintptr_t>(xpos) | reinterpret_cast<uintptr_t>(ypos)) & 15) == 0 && (xps & 3) == 0 && (yps & 3) == 0 &&
                          (reinterpret_cast<uintptr_t>(dest) & 7) == 0 && (n & 3) == 0 && (m & 3) == 0;
     (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
-    auto go = [&](auto kern, int kpl) {
-        const size_t lds = (size_t)(sot::align4(sot::imax(sot::sort16_capacity(sot::sort16_npad(64 * kpl)), wave_sort_scratch(kpl))) + sot::align4(sot::sort16_capacity(sot::sort16_npad(64 * kpl)))) * 4 * 4;   // 4 waves x (idx / scratch | key)
-        static GridCache cache;   // (one per lambda instantiation, i.e. per kernel)
-        allow_full_lds_once(cache, reinterpret_cast<const void*>(kern));
+    auto go = [&](auto kpl_tag, auto full, auto vec) {
+        constexpr int KP = decltype(kpl_tag)::value;
+        constexpr auto kern = sot_rowpos_sort_kernel<KP, decltype(full)::value, decltype(vec)::value>;
+        constexpr size_t lds = (size_t)(wave_sort_idx_cap<KP>() + wave_sort_key_cap<KP>()) * 4 * 4;   // 4 waves x (idx / scratch | key)
+        allow_full_lds_once<kern>();
         int per_cu = (int)(kLdsLimit / lds);
         if (per_cu > kRowposSortMaxWg) per_cu = kRowposSortMaxWg;   // four-wave workgroups: one wave of each per SIMD, at most 16 waves per CU
-        const int64_t groups = (2 * B + 3) / 4, cap = (int64_t)device_cu_count() * per_cu;   // one wave per array
-        hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap)), dim3(256), lds, s, xpos, ypos, B, n, m, xps, yps, dest);
+        hipLaunchKernelGGL(kern, dim3(capped_grid((2 * B + 3) / 4, per_cu)), dim3(256), lds, s, xpos, ypos, B, n, m, xps, yps, dest);   // one wave per array
     };
     auto pick = [&](auto kpl_tag) {
         constexpr int KP = decltype(kpl_tag)::value;
-        if (aligned && n == 64 * KP && m == 64 * KP) go(sot_rowpos_sort_kernel<KP, true, true>, KP);
-        else if (aligned) go(sot_rowpos_sort_kernel<KP, false, true>, KP);
-        else go(sot_rowpos_sort_kernel<KP, false, false>, KP);
+        if (aligned && n == 64 * KP && m == 64 * KP) go(kpl_tag, std::true_type{}, std::true_type{});
+        else if (aligned) go(kpl_tag, std::false_type{}, std::true_type{});
+        else go(kpl_tag, std::false_type{}, std::false_type{});
     };
     if (N <= 512) pick(std::integral_constant<int, 8>{});
     else if (N <= 1024) pick(std::integral_constant<int, 16>{});
     else pick(std::integral_constant<int, 32>{});
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return launch_status();
 }
 
 int launch_prepare(const float* xpos, const float* ypos, int n, int m, float* sx, float* sy, int* px, int* py, int* ident,
@@ -413,18 +413,17 @@ int launch_prepare(const float* xpos, const float* ypos, int n, int m, float* sx
 {
     const int npad = sort16_npad(n > m ? n : m);
     if (npad > 16 * 1024) return SOT_ERR_UNSUPPORTED_SIZE;
-    const size_t prep_lds = (size_t)((sort16_capacity(npad) + 3) & ~3) * 8 + 16 + 64;   // + the flag's slot + 16 partial maxima
+    const size_t prep_lds = (size_t)align4(sort16_capacity(npad)) * 8 + 16 + 64;   // + the flag's slot + 16 partial maxima
     if (prep_lds > kLdsLimit) return SOT_ERR_UNSUPPORTED_SIZE;
-    static GridCache cache, cache_unit;
     (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
-    if (unit) {
-        allow_full_lds_once(cache_unit, reinterpret_cast<const void*>(sot_prepare_positions_kernel<true>));
-        hipLaunchKernelGGL(sot_prepare_positions_kernel<true>, dim3(2), dim3(1024), prep_lds, s, xpos, ypos, n, m, sx, sy, px, py, ident);
-    } else {
-        allow_full_lds_once(cache, reinterpret_cast<const void*>(sot_prepare_positions_kernel<false>));
-        hipLaunchKernelGGL(sot_prepare_positions_kernel<false>, dim3(2), dim3(1024), prep_lds, s, xpos, ypos, n, m, sx, sy, px, py, ident);
-    }
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    auto go = [&](auto unit_tag) {
+        constexpr auto kern = sot_prepare_positions_kernel<decltype(unit_tag)::value>;
+        allow_full_lds_once<kern>();
+        hipLaunchKernelGGL(kern, dim3(2), dim3(1024), prep_lds, s, xpos, ypos, n, m, sx, sy, px, py, ident);
+    };
+    if (unit) go(std::true_type{});
+    else go(std::false_type{});
+    return launch_status();
 }
 
 // validation, config choice, optional position preparation, persistent-grid sizing
@@ -506,7 +505,7 @@ int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, fl
     // compile-time-length kernel with a position copy of its own per row (sot_full_fwd.hpp: RP)
     const bool full_rp = l.rowpos && l.a.perm_in != nullptr && !quant && (pr->n == 2048 || pr->n == 1024 || pr->n == 512) && pr->m == pr->n && l.vec && (pr->flags & SOT_FLAG_REQUIRE_SORT) &&
                    (reinterpret_cast<uintptr_t>(l.a.perm_in) & 15) == 0 && !(pr->flags & (SOT_FLAG_PRENORMALIZED | SOT_FLAG_NO_SPECIALIZE));
-    if (full_rp) return dispatch_forward_full_rowpos(l.pm, l.a, l.s) == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    if (full_rp) return launch_status(dispatch_forward_full_rowpos(l.pm, l.a, l.s));
     // p = 1 on one grid shared by both measures, no cutoff: the merge-free kernel (sot_full_fwd.hpp: sot_area_full_kernel)
     const bool area = (full || full_rt) && l.pm == 1 && (pr->flags & SOT_FLAG_SAME_GRID) && !(pr->flags & (SOT_FLAG_LIMIT_Q | SOT_FLAG_NO_AREA));
     const hipError_t e = area       ? (full ? dispatch_area_full(l.a, l.s) : dispatch_area_full_rt(l.a, l.s))
@@ -514,7 +513,7 @@ int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, fl
                          : full_rt  ? dispatch_forward_full_rt(l.pm, l.a, l.s)
                          : l.rowpos ? dispatch_forward<true>(l.cfg, quant, l.pm, l.vec, l.a, l.lds, l.want, l.block, l.s)
                                     : dispatch_forward<false>(l.cfg, quant, l.pm, l.vec, l.a, l.lds, l.want, l.block, l.s);
-    return e == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 // row_loss_out (loss-and-gradient form): the kernels that can also emit the row losses do so and *fused is set; the caller
@@ -556,7 +555,7 @@ int run_backward(const sot_problem* pr, const float* grad_row, int64_t grad_row_
                          : full_rt  ? dispatch_backward_full_rt(l.pm, b, l.s)
                          : l.rowpos ? dispatch_backward<true>(l.cfg, l.pm, l.vec, b, l.lds, l.want, l.block, l.s)
                                     : dispatch_backward<false>(l.cfg, l.pm, l.vec, b, l.lds, l.want, l.block, l.s);
-    return e == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 }  // namespace sot
@@ -635,22 +634,25 @@ size_t sot_workspace_bytes(const sot_problem* prob)
     return sot::ws_layout(prob->n, prob->m).total;
 }
 
-int sot_prepare_positions(const float* xpos, const float* ypos, int32_t n, int32_t m, float* xpos_sorted, float* ypos_sorted,
-                          int32_t* xperm, int32_t* yperm, int32_t* perm_is_identity, void* stream)
+static int prepare_positions(const float* xpos, const float* ypos, int32_t n, int32_t m, float* xpos_sorted, float* ypos_sorted,
+                             int32_t* xperm, int32_t* yperm, int32_t* perm_is_identity, void* stream, bool unit)
 {
     if (n < 1 || m < 1) return SOT_ERR_BAD_SHAPE;
     if (!xpos || !ypos || !xpos_sorted || !ypos_sorted || !xperm || !yperm || !perm_is_identity) return SOT_ERR_NULL_POINTER;
     return sot::launch_prepare(xpos, ypos, n, m, xpos_sorted, ypos_sorted, xperm, yperm, perm_is_identity,
-                               reinterpret_cast<hipStream_t>(stream), false);
+                               reinterpret_cast<hipStream_t>(stream), unit);
+}
+
+int sot_prepare_positions(const float* xpos, const float* ypos, int32_t n, int32_t m, float* xpos_sorted, float* ypos_sorted,
+                          int32_t* xperm, int32_t* yperm, int32_t* perm_is_identity, void* stream)
+{
+    return prepare_positions(xpos, ypos, n, m, xpos_sorted, ypos_sorted, xperm, yperm, perm_is_identity, stream, false);
 }
 
 int sot_prepare_unit_positions(const float* xpos, const float* ypos, int32_t n, int32_t m, float* xpos_sorted, float* ypos_sorted,
                                int32_t* xperm, int32_t* yperm, int32_t* perm_is_identity, void* stream)
 {
-    if (n < 1 || m < 1) return SOT_ERR_BAD_SHAPE;
-    if (!xpos || !ypos || !xpos_sorted || !ypos_sorted || !xperm || !yperm || !perm_is_identity) return SOT_ERR_NULL_POINTER;
-    return sot::launch_prepare(xpos, ypos, n, m, xpos_sorted, ypos_sorted, xperm, yperm, perm_is_identity,
-                               reinterpret_cast<hipStream_t>(stream), true);
+    return prepare_positions(xpos, ypos, n, m, xpos_sorted, ypos_sorted, xperm, yperm, perm_is_identity, stream, true);
 }
 
 int sot_w1d_forward(const sot_problem* prob, float* row_loss, void* workspace, size_t workspace_bytes, void* stream)
@@ -674,7 +676,7 @@ int sot_w1d_reduce_mean(const float* row_loss, int64_t B, double denom, int appl
     (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
     hipLaunchKernelGGL(sot::sot_reduce_mean_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), row_loss, B,
                        denom, apply_hinge, hinge_threshold, mean_out, sum_out);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_w1d_backward(const sot_problem* prob, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* grad_x,
@@ -719,7 +721,7 @@ int sot_scale_inplace(float* data, int64_t count, const float* scalar, void* str
     const int grid = (int)(need < 256 * 16 ? need : 256 * 16);
     (void)hipGetLastError();
     hipLaunchKernelGGL(sot::sot_scale_inplace_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), data, count, scalar);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_w1d_loss(const sot_problem* prob, float* row_loss, double denom, int apply_hinge, float hinge_threshold, float* mean_out,
@@ -772,22 +774,20 @@ int sot_segmented_sort(const float* keys, int64_t B, int32_t n, int64_t row_stri
     }
     const int npad = sot::sort16_npad((int)n);
     if (npad > 16 * 1024) return SOT_ERR_UNSUPPORTED_SIZE;   // one block of 16 elements per thread
-    const size_t lds = (size_t)((sot::sort16_capacity(npad) + 3) & ~3) * 8;
+    const size_t lds = (size_t)sot::align4(sot::sort16_capacity(npad)) * 8;
     if (lds > sot::kLdsLimit) return SOT_ERR_UNSUPPORTED_SIZE;
-    static sot::GridCache cache;
-    sot::allow_full_lds_once(cache, reinterpret_cast<const void*>(sot::sot_segmented_sort_kernel));
+    sot::allow_full_lds_once<sot::sot_segmented_sort_kernel>();
     int block = 64;                                    // one thread per block of 16 elements (whole wavefronts)
     while (block < 1024 && npad > 16 * block) block <<= 1;
     int per_cu = (int)(sot::kLdsLimit / lds);
     const int wave_cap = 32 / (block / 64);            // at most 8 wavefronts per SIMD
     if (per_cu > wave_cap) per_cu = wave_cap;
     if (per_cu > 16) per_cu = 16;
-    int64_t cap = (int64_t)sot::device_cu_count() * per_cu;
-    const int grid = (int)(B < cap ? B : cap);
+    const int grid = sot::capped_grid(B, per_cu);
     (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
     hipLaunchKernelGGL(sot::sot_segmented_sort_kernel, dim3(grid), dim3(block), lds, reinterpret_cast<hipStream_t>(stream), keys, B,
                        (int)n, row_stride, sorted_keys, indices);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
-// sot_launch.hpp -- host side shared by the row-kernel objects: launch configuration (pick_cfg), resident-grid caches, argument
-// validation, workspace layout, kernel-attached timing, the launch of a persistent kernel (launch_persistent), the switch from the
-// run-time cost / cutoff / square_dist mode to template arguments (with_mode), and the declarations of what one object calls in another.
+// sot_launch.hpp -- host side shared by the row-kernel objects, on top of the library's launch layer (sot_host.hpp): launch configuration
+// (pick_cfg), argument validation, workspace layout, kernel-attached timing and the profiled launch of a persistent kernel, the switch from
+// the run-time cost / cutoff / square_dist mode to template arguments (with_mode), and the declarations of what one object calls in another.
 #pragma once
+#include "sot_host.hpp"
 #include "sot_rows.hpp"
 
 namespace sot {
@@ -9,41 +10,6 @@ namespace sot {
 // ---------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------
-constexpr size_t kLdsLimit = 160 * 1024;
-
-// Allow a kernel to use up to the CU's full 160 KiB of dynamic LDS; leaves no sticky error behind.
-static inline void allow_full_lds(const void* kernel)
-{
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit) != hipSuccess)
-        (void)hipGetLastError();
-}
-
-// Launch state is kept PER DEVICE and behind a mutex: a process may use several GPUs (the binding switches devices per
-// call), and calls arrive from several host threads (autograd runs backward on its own thread; ctypes drops the GIL).
-constexpr int kMaxDevices = 64;
-static inline int current_device()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    return dev;
-}
-
-static inline int device_cu_count()
-{
-    static std::mutex mu;
-    static int cus[kMaxDevices] = {};
-    const int dev = current_device();
-    const bool cacheable = dev >= 0 && dev < kMaxDevices;
-    std::lock_guard<std::mutex> lock(mu);
-    if (cacheable && cus[dev] > 0) return cus[dev];
-    hipDeviceProp_t prop;
-    int n = 256;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n = prop.multiProcessorCount;
-    else (void)hipGetLastError();
-    if (cacheable) cus[dev] = n;
-    return n;
-}
-
 struct LaunchCfg { int G, CPT; };
 
 // Row-group geometries: (threads per row, contiguous elements per thread).  G*CPT >= max(n, m).
@@ -64,59 +30,6 @@ static inline bool pick_cfg(int n, int m, bool rowpos, bool with_grad, LaunchCfg
         return true;
     }
     return false;
-}
-
-// Persistent grid: exactly as many workgroups as are co-resident (registers, LDS and wave slots all
-// taken into account by the occupancy query), never more than there are row groups.
-template <typename Kernel>
-static inline int resident_grid(Kernel kern, int block, size_t lds, int64_t want)
-{
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, lds) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    const int64_t cap = (int64_t)device_cu_count() * per_cu;
-    return (int)(want < cap ? want : cap);
-}
-
-// resident_grid() of one kernel instantiation, cached per device (and per LDS size: the generic kernels' LDS request
-// depends on n, m); the first use on a device also opts the kernel in to the CU's full LDS THERE (hipFuncSetAttribute
-// applies to the current device only).  One cache per kernel: launch_persistent below owns it.
-struct GridCache {
-    std::mutex mu;
-    struct Entry { size_t lds; int grid; bool attr; } e[kMaxDevices] = {};
-};
-
-// Grid of a persistent kernel whose workgroups stride over `want` row groups, at most `cap` of them resident (some run one
-// round more: splitting the rows evenly over fewer workgroups was measured 5 % slower for the training form).
-static inline int persistent_grid(int64_t want, int cap)
-{
-    return want <= cap ? (int)want : cap;
-}
-
-template <typename Kernel>
-static inline int cached_resident_grid(GridCache& gc, Kernel kern, int block, size_t lds)
-{
-    const int dev = current_device();
-    if (dev < 0 || dev >= kMaxDevices) {
-        allow_full_lds(reinterpret_cast<const void*>(kern));
-        return resident_grid(kern, block, lds, INT32_MAX);
-    }
-    std::lock_guard<std::mutex> lock(gc.mu);
-    GridCache::Entry& e = gc.e[dev];
-    if (!e.attr) { allow_full_lds(reinterpret_cast<const void*>(kern)); e.attr = true; }
-    if (e.grid == 0 || e.lds != lds) { e.grid = resident_grid(kern, block, lds, INT32_MAX); e.lds = lds; }
-    return e.grid;
-}
-
-// once per device: opt `kernel` in to the full LDS (kernels launched with a fixed grid)
-static inline void allow_full_lds_once(GridCache& gc, const void* kernel)
-{
-    const int dev = current_device();
-    if (dev < 0 || dev >= kMaxDevices) { allow_full_lds(kernel); return; }
-    std::lock_guard<std::mutex> lock(gc.mu);
-    if (!gc.e[dev].attr) { allow_full_lds(kernel); gc.e[dev].attr = true; }
 }
 
 static inline int validate(const sot_problem* pr)
@@ -164,18 +77,16 @@ static inline void launch_maybe_profiled(Kernel kern, int grid, int block, size_
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, s, a);
 }
 
-// The launch of a persistent kernel: its grid of resident workgroups from a cache of its own (one per kernel `Kern`, per device inside;
-// function-local static: thread-safe initialisation), never more workgroups than the `want` row groups, and the launch's own error.
-// PROFILED: the launch goes through launch_maybe_profiled, i.e. it consumes an armed sot_profile_next_launch (the full-row kernels only).
+// launch_persistent (sot_host.hpp) for the full-row kernels: the launch goes through launch_maybe_profiled, i.e. it consumes an armed
+// sot_profile_next_launch.
 // A workgroup's second and later rows are tested in tests/test_row_loop_gpu.py, on batches that force them; a new row kernel adds a line to its CASES.
-template <auto Kern, bool PROFILED = false, class Args>
-static inline hipError_t launch_persistent(const Args& args, size_t lds, int64_t want, int block, hipStream_t s)
+template <auto Kern, class Args>
+static inline hipError_t launch_persistent_profiled(const Args& args, size_t lds, int64_t want, int block, hipStream_t s)
 {
     static GridCache cache;
     const int grid = persistent_grid(want, cached_resident_grid(cache, Kern, block, lds));
     (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
-    if constexpr (PROFILED) launch_maybe_profiled(Kern, grid, block, lds, s, args);
-    else hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, s, args);
+    launch_maybe_profiled(Kern, grid, block, lds, s, args);
     return hipGetLastError();
 }
 

@@ -531,7 +531,7 @@ int sot_w1d_mixed_forward(const sot_problem* prob, float* row_loss, void* worksp
     if (prob->B == 0) return SOT_OK;
     l.a.row_loss = row_loss;
     sot::MixedGradArgs b{};
-    return sot::dispatch_mixed<0>(l, b) == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status(sot::dispatch_mixed<0>(l, b));
 }
 
 int sot_w1d_mixed_backward(const sot_problem* prob, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* grad_x,
@@ -543,7 +543,7 @@ int sot_w1d_mixed_backward(const sot_problem* prob, const float* grad_row, int64
     if (prob->B == 0 || (grad_x == nullptr && grad_y == nullptr)) return SOT_OK;
     sot::MixedGradArgs b{};
     b.f = l.a; b.grad_row = grad_row; b.grad_row_stride = grad_row_stride; b.grad_scale = grad_scale; b.gx = grad_x; b.gy = grad_y;
-    return sot::dispatch_mixed<1>(l, b) == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status(sot::dispatch_mixed<1>(l, b));
 }
 
 int sot_w1d_mixed_position_grad(const sot_problem* prob, const float* grad_row, int64_t grad_row_stride, float grad_scale,
@@ -556,7 +556,7 @@ int sot_w1d_mixed_position_grad(const sot_problem* prob, const float* grad_row, 
     if (prob->B == 0) return SOT_OK;
     sot::MixedGradArgs b{};
     b.f = l.a; b.grad_row = grad_row; b.grad_row_stride = grad_row_stride; b.grad_scale = grad_scale; b.gpos = grad_pos;
-    return sot::dispatch_mixed<2>(l, b) == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status(sot::dispatch_mixed<2>(l, b));
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "../../include/sot_hip.h"
+#include "sot_host.hpp"
 #include "sot_wave_fft.hpp"
 
 namespace sot_mss {
@@ -685,6 +685,17 @@ static int fill(const float* target, int64_t stride_t, const float* value, int64
     return SOT_OK;
 }
 
+// `waves` wavefronts of the kernel Kern (mss_fused_kernel, mss_metric_kernel) in workgroups of WG_WAVES
+template <auto Kern, int WG_WAVES, class Args>
+static void launch_waves(int waves, hipStream_t st, const Args& a)
+{
+    sot::allow_full_lds_once<Kern>();
+    hipLaunchKernelGGL(Kern, dim3((unsigned)((waves + WG_WAVES - 1) / WG_WAVES)), dim3(64 * WG_WAVES), lds_bytes(WG_WAVES), st, a);
+}
+
+template <bool GRAD, int KIND, int WG_WAVES>
+static void launch_fused(int waves, hipStream_t st, const MssArgs& a) { launch_waves<mss_fused_kernel<GRAD, KIND, WG_WAVES>, WG_WAVES>(waves, st, a); }
+
 }  // namespace sot_mss
 
 extern "C" {
@@ -720,34 +731,22 @@ int sot_mss_loss_and_grad(const float* target, int64_t target_row_stride, const 
     a.loss = loss; a.grad = grad_value; a.want_grad = grad_value != nullptr; a.post_scale = post_scale;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     (void)hipGetLastError();
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
     const int kind = (l2 == 0 && !(logmag_weight > 0.0f)) ? 0 : 1;     // the paper's configuration (L1 on the magnitudes) has its own instantiation
-    const int tasks = a.task_base[n_scales], slots = 16 * cus;         // one wave per task slot: 16 waves per CU (LDS)
+    const int tasks = a.task_base[n_scales], slots = 16 * sot::device_cu_count();   // one wave per task slot: 16 waves per CU (LDS)
     const bool small = tasks <= slots;                                 // a single round: 4-wave workgroups spread it evenly
-    void (*kern)(const MssArgs) =
-        small ? (kind == 0 ? (a.want_grad ? mss_fused_kernel<true, 0, 4> : mss_fused_kernel<false, 0, 4>)
-                           : (a.want_grad ? mss_fused_kernel<true, 1, 4> : mss_fused_kernel<false, 1, 4>))
-              : (kind == 0 ? (a.want_grad ? mss_fused_kernel<true, 0, 16> : mss_fused_kernel<false, 0, 16>)
-                           : (a.want_grad ? mss_fused_kernel<true, 1, 16> : mss_fused_kernel<false, 1, 16>));
-    const int wg_waves = small ? 4 : 16;     // LDS: tables 16.4 KB + 8.7 KB per wave: three 4-wave workgroups or one of 16 waves per CU
-    static bool attr_done[64][8] = {};
-    const int which = 4 * (small ? 1 : 0) + 2 * kind + a.want_grad;
-    if (dev < 0 || dev >= 64 || !attr_done[dev][which]) {   // idempotent per device; a benign race sets it twice
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(wg_waves)) != hipSuccess)
-            (void)hipGetLastError();
-        if (dev >= 0 && dev < 64) attr_done[dev][which] = true;
-    }
+    // LDS: tables 16.4 KB + 8.7 KB per wave: three 4-wave workgroups or one of 16 waves per CU
+    void (*launch)(int, hipStream_t, const MssArgs&) =
+        small ? (kind == 0 ? (a.want_grad ? launch_fused<true, 0, 4> : launch_fused<false, 0, 4>)
+                           : (a.want_grad ? launch_fused<true, 1, 4> : launch_fused<false, 1, 4>))
+              : (kind == 0 ? (a.want_grad ? launch_fused<true, 0, 16> : launch_fused<false, 0, 16>)
+                           : (a.want_grad ? launch_fused<true, 1, 16> : launch_fused<false, 1, 16>));
     // persistent grid: at most 16 waves per CU; wave g takes tasks g, g + (waves of the grid), ...
-    const int waves_needed = tasks < slots ? tasks : slots;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((waves_needed + wg_waves - 1) / wg_waves)), dim3(64 * wg_waves), lds_bytes(wg_waves), st, a);
-    if (hipGetLastError() != hipSuccess) return SOT_ERR_LAUNCH;
+    launch(tasks < slots ? tasks : slots, st, a);
+    if (sot::launch_status() != SOT_OK) return SOT_ERR_LAUNCH;
     const int64_t work = a.want_grad ? (batch * ((((samples + 1) / 2) + 255) / 256) + 1) / 2 : 1;      // one workgroup per TWO (clip, 256 packed points) blocks
     const int64_t blocks = (work < 16384 ? (work < 1 ? 1 : work) : 16384) + ((a.want_grad && !per_clip) ? 1 : 0);      // + the loss workgroup
     hipLaunchKernelGGL(mss_finish_kernel, dim3((unsigned)blocks), dim3(kFinishThreads), 0, st, a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 }  // extern "C"
@@ -790,18 +789,6 @@ static int fill_metrics(const float* target, int64_t stride_t, const float* valu
     return SOT_OK;
 }
 
-// The dynamic-LDS opt-in of one kernel: its own state per kernel instantiation (a static of this template), per device; idempotent, a benign
-// race sets it twice.
-template <int kWaves>
-static void metric_lds_opt_in(int dev)
-{
-    static bool done[64] = {};
-    if (dev >= 0 && dev < 64 && done[dev]) return;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mss_metric_kernel<kWaves>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kWaves)) != hipSuccess)
-        (void)hipGetLastError();
-    if (dev >= 0 && dev < 64) done[dev] = true;
-}
-
 }  // namespace sot_mss
 
 extern "C" {
@@ -835,28 +822,15 @@ int sot_spec_metrics(const float* target, int64_t target_row_stride, const float
     a.out = out;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     (void)hipGetLastError();
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) { (void)hipGetLastError(); cus = 256; }
     // the engine's two grid forms (sot_mss_loss_and_grad): 4-wave workgroups for one round of 16 x CUs wave slots, 16-wave workgroups beyond
-    const int tasks = a.task_base[n_sizes], slots = 16 * cus;
-    const bool small = tasks <= slots;
-    const int wg_waves = small ? 4 : 16;
-    const int waves_needed = tasks < slots ? tasks : slots;
-    const dim3 grid((unsigned)((waves_needed + wg_waves - 1) / wg_waves));
-    if (small) {
-        metric_lds_opt_in<4>(dev);
-        hipLaunchKernelGGL(mss_metric_kernel<4>, grid, dim3(64 * 4), lds_bytes(4), st, a);
-    } else {
-        metric_lds_opt_in<16>(dev);
-        hipLaunchKernelGGL(mss_metric_kernel<16>, grid, dim3(64 * 16), lds_bytes(16), st, a);
-    }
-    if (hipGetLastError() != hipSuccess) return SOT_ERR_LAUNCH;
+    const int tasks = a.task_base[n_sizes], slots = 16 * sot::device_cu_count();
+    if (tasks <= slots) launch_waves<mss_metric_kernel<4>, 4>(tasks, st, a);
+    else launch_waves<mss_metric_kernel<16>, 16>(slots, st, a);
+    if (sot::launch_status() != SOT_OK) return SOT_ERR_LAUNCH;
     const int64_t clip_blocks = (batch + kFinishThreads - 1) / kFinishThreads;
     const unsigned fx = per_clip ? (unsigned)(clip_blocks < 4096 ? clip_blocks : 4096) : 1u;
     hipLaunchKernelGGL(metric_finish_kernel, dim3(fx, (unsigned)n_groups), dim3(kFinishThreads), 0, st, a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 #ifdef MSS_STAMPS

@@ -17,9 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include <mutex>
 
-#include "../../include/sot_hip.h"
+#include "sot_host.hpp"
 
 namespace sot_osc {
 
@@ -428,8 +427,6 @@ inline size_t segment_array_bytes(int64_t batch, int64_t samples, int K)
     return (size_t)batch * (size_t)((samples + S - 1) / S) * (size_t)K * sizeof(double);
 }
 
-inline bool launched() { return hipGetLastError() == hipSuccess; }
-
 // fills a.phase0 with the phase of every sinusoid at the start of every segment
 inline bool launch_segment_starts(const OscArgs& a, hipStream_t st)
 {
@@ -443,7 +440,7 @@ inline bool launch_segment_starts(const OscArgs& a, hipStream_t st)
         const unsigned sgrid = (unsigned)((a.batch * a.sinusoids + kThreads - 1) / kThreads);
         hipLaunchKernelGGL(oscillator_scan_kernel, dim3(sgrid), dim3(kThreads), 0, st, a.phase0, a.batch, a.nseg, a.sinusoids, 0);
     }
-    return launched();
+    return sot::launch_status() == SOT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -635,7 +632,7 @@ int sot_synth_envelopes_forward(const float* amp_frames, const float* freq_frame
     (void)hipGetLastError();
     hipLaunchKernelGGL(synth_envelopes_forward_kernel, dim3((unsigned)(want < cap ? want : cap), (unsigned)(batch < 65535 ? batch : 65535)), dim3(kThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_synth_envelopes_backward(const float* amp_frames, const float* freq_frames, const float* window, int64_t batch, int frames,
@@ -656,7 +653,7 @@ int sot_synth_envelopes_backward(const float* amp_frames, const float* freq_fram
     (void)hipGetLastError();
     hipLaunchKernelGGL(synth_envelopes_backward_kernel, dim3((unsigned)(batch * frames)), dim3(kThreads), lds,
                        reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 
@@ -690,7 +687,7 @@ int sot_oscillator_bank_forward(const float* freq, const float* amp, int64_t bat
     if (!launch_segment_starts(a, st)) return SOT_ERR_LAUNCH;
     hipLaunchKernelGGL(oscillator_tile_kernel<kForward>, dim3((unsigned)(batch * a.nseg)), dim3(kThreads),
                        lds_bytes(a.seg_len, sinusoids, kForward), st, a);
-    return launched() ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_oscillator_bank_backward(const float* freq, const float* amp, int64_t batch, int64_t samples, int sinusoids, float sample_rate,
@@ -726,7 +723,7 @@ int sot_oscillator_bank_backward(const float* freq, const float* amp, int64_t ba
         }
         hipLaunchKernelGGL(oscillator_suffix_kernel, dim3(grid), dim3(kThreads), lds_bytes(a.seg_len, sinusoids, kTotals), st, a);
     }
-    return launched() ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 // backward workspace: [segment start phases][segment dphi totals][wtab: frames x 3 hop doubles][partial sums x 2][atab: frames x 3 hop floats]
@@ -780,7 +777,7 @@ int sot_synth_forward(const float* amp_frames, const float* freq_frames, const f
     if (!launch_segment_starts(a, st)) return SOT_ERR_LAUNCH;
     hipLaunchKernelGGL((oscillator_tile_kernel<kForward, true>), dim3((unsigned)(batch * a.nseg)), dim3(kThreads),
                        lds_bytes(a.seg_len, sinusoids, kForward), st, a);
-    return launched() ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 size_t sot_synth_tap_table_bytes(int frames, int64_t samples)
@@ -800,7 +797,7 @@ int sot_synth_tap_tables(const float* window, int frames, int64_t samples, void*
     (void)hipGetLastError();
     hipLaunchKernelGGL(synth_tap_table_kernel, dim3((unsigned)frames), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), e, wtab,
                        reinterpret_cast<float*>(wtab + 3 * (size_t)samples));
-    return launched() ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_synth_backward(const float* amp_frames, const float* freq_frames, const float* window, int64_t batch, int frames, int sinusoids,
@@ -834,25 +831,14 @@ int sot_synth_backward(const float* amp_frames, const float* freq_frames, const 
     a.nslot = frame_slots(a.seg_len, a.ctl.hop);
     a.grad_audio = grad_audio;
     const size_t lds = lds_bytes_frames(a.seg_len, sinusoids, a.ctl.hop);
-    if (lds > 160 * 1024) return SOT_ERR_UNSUPPORTED_SIZE;
+    if (lds > sot::kLdsLimit) return SOT_ERR_UNSUPPORTED_SIZE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(batch * a.nseg);
     (void)hipGetLastError();
     if (!workspace_from_forward && !launch_segment_starts(a, st)) return SOT_ERR_LAUNCH;
     if (tap_tables == nullptr) hipLaunchKernelGGL(synth_tap_table_kernel, dim3((unsigned)frames), dim3(kThreads), 0, st, a.ctl, wtab, atab);
-    auto kern = oscillator_tile_kernel<kBackwardFrames, true>;
-    if (lds > 64 * 1024) {   // opt this kernel in to the full LDS once per DEVICE (the attribute is per device; setting it twice is harmless)
-        static std::mutex mu;
-        static bool done[64] = {};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); dev = -1; }
-        std::lock_guard<std::mutex> lock(mu);
-        if (dev < 0 || !done[dev]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                (void)hipGetLastError();
-            if (dev >= 0) done[dev] = true;
-        }
-    }
+    constexpr auto kern = oscillator_tile_kernel<kBackwardFrames, true>;
+    if (lds > 64 * 1024) sot::allow_full_lds_once<kern>();
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, st, a);
     if (a.part_freq != nullptr && a.nseg > 1 && a.scanned) {
         const unsigned sgrid = (unsigned)((batch * sinusoids + kThreads - 1) / kThreads);
@@ -860,7 +846,7 @@ int sot_synth_backward(const float* amp_frames, const float* freq_frames, const 
     }
     hipLaunchKernelGGL(synth_frames_reduce_kernel, dim3((unsigned)(batch * frames)), dim3(64), sizeof(double) * (size_t)sinusoids, st, a,
                        grad_amp_frames, grad_freq_frames);
-    return launched() ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 }  // extern "C"

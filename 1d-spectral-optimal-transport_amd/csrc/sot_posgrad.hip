@@ -210,7 +210,7 @@ int run_position_grad(const sot_problem* pr, const float* grad_row, int64_t grad
     b.f = l.a; b.grad_row = grad_row; b.grad_row_stride = grad_row_stride; b.grad_scale = grad_scale; b.gxp = gxp; b.gyp = gyp;
     const hipError_t e = l.rowpos ? dispatch_position_grad<true>(l.cfg, b, lds, l.want, l.block, l.s)
                                   : dispatch_position_grad<false>(l.cfg, b, lds, l.want, l.block, l.s);
-    return e == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 // out[c] = sum_r rows[r * stride + c] in a fixed order (the sum over the batch that autograd attaches to a position row shared by
@@ -238,7 +238,7 @@ int run_column_sum(const float* rows, int64_t B, int n, int64_t stride, float* o
 {
     (void)hipGetLastError();
     hipLaunchKernelGGL(sot_column_sum_kernel, dim3((n + 15) / 16), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), rows, B, n, stride, out);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return launch_status();
 }
 
 }  // namespace sot

@@ -242,7 +242,7 @@ int run_quantiles_backward(const sot_problem* pr, const float* gUq, const float*
     b.f = l.a; b.gUq = gUq; b.gVq = gVq; b.gQ = gQ; b.gU = gU; b.gV = gV; b.gx = gx; b.gy = gy; b.gxp = gxp; b.gyp = gyp;
     const hipError_t e = l.rowpos ? dispatch_quantiles_backward<true>(l.cfg, b, lds, l.want, l.block, l.s)
                                   : dispatch_quantiles_backward<false>(l.cfg, b, lds, l.want, l.block, l.s);
-    return e == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return launch_status(e);
 }
 
 }  // namespace sot

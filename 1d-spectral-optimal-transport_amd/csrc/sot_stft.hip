@@ -19,11 +19,11 @@
 // gradient once.  (4 frames per group: 2.75 x, but half the workgroups; the same time at n_fft 2048, 20 % slower over
 // the six scales of MSSLoss.)
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 
-#include "../../include/sot_hip.h"
+#include "sot_host.hpp"
 #include "sot_wave_fft.hpp"
 
 namespace sot_stft {
@@ -1311,40 +1311,24 @@ static int fill_args(const float* audio, int64_t batch, int64_t samples, int64_t
 #define SOT_STFT_LAUNCH(KERNEL, work, extra_lds_per_slot, st, a)                                                              \
     do {                                                                                                                      \
         switch ((a).logm) {                                                                                                   \
-            case 5: launch_slots<5>(KERNEL<5>, work, extra_lds_per_slot, st, a); break;                                       \
-            case 6: launch_slots<6>(KERNEL<6>, work, extra_lds_per_slot, st, a); break;                                       \
-            case 7: launch_slots<7>(KERNEL<7>, work, extra_lds_per_slot, st, a); break;                                       \
-            case 8: launch_slots<8>(KERNEL<8>, work, extra_lds_per_slot, st, a); break;                                       \
-            case 9: launch_slots<9>(KERNEL<9>, work, extra_lds_per_slot, st, a); break;                                       \
-            case 10: launch_slots<10>(KERNEL<10>, work, extra_lds_per_slot, st, a); break;                                    \
-            default: launch_slots<11>(KERNEL<11>, work, extra_lds_per_slot, st, a); break;                                    \
+            case 5: launch_slots<KERNEL<5>, 5>(work, extra_lds_per_slot, st, a); break;                                       \
+            case 6: launch_slots<KERNEL<6>, 6>(work, extra_lds_per_slot, st, a); break;                                       \
+            case 7: launch_slots<KERNEL<7>, 7>(work, extra_lds_per_slot, st, a); break;                                       \
+            case 8: launch_slots<KERNEL<8>, 8>(work, extra_lds_per_slot, st, a); break;                                       \
+            case 9: launch_slots<KERNEL<9>, 9>(work, extra_lds_per_slot, st, a); break;                                       \
+            case 10: launch_slots<KERNEL<10>, 10>(work, extra_lds_per_slot, st, a); break;                                    \
+            default: launch_slots<KERNEL<11>, 11>(work, extra_lds_per_slot, st, a); break;                                    \
         }                                                                                                                     \
     } while (0)
 
-template <int LOGM>
-static void launch_slots(void (*kernel)(const StftArgs), int64_t work, size_t extra_lds_per_slot, hipStream_t st, const StftArgs& a)
+template <auto Kernel, int LOGM>
+static void launch_slots(int64_t work, size_t extra_lds_per_slot, hipStream_t st, const StftArgs& a)
 {
     using G = Geo<LOGM>;
     const size_t lds = G::lds_points * sizeof(float2) + (size_t)G::slots * extra_lds_per_slot;
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-            (void)hipGetLastError();
-    }
+    if (lds > 64 * 1024) sot::allow_full_lds_once<Kernel>();
     const unsigned grid = (unsigned)((work + G::slots - 1) / G::slots);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds, st, a);
-}
-
-static int cu_count()
-{
-    static std::atomic<int> cus[64];   // zero-initialised; per device, written with the same value by whoever gets there first
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
-    int v = cus[dev].load(std::memory_order_relaxed);
-    if (v == 0) {
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) { (void)hipGetLastError(); v = 256; }
-        cus[dev].store(v, std::memory_order_relaxed);
-    }
-    return v;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(kThreads), lds, st, a);
 }
 
 // the persistent forward kernel on as many workgroups as stay resident (LDS / 2048 threads per CU)
@@ -1353,19 +1337,9 @@ static void launch_forward_persistent(int64_t work, hipStream_t st, const StftAr
 {
     using G = Geo<LOGM>;
     const size_t lds = ((size_t)G::slots * G::zpoints + G::m) * sizeof(float2);
-    static std::atomic<int> per_cu_cache[64];   // per device, as in cu_count()
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); dev = 0; }
-    int per_cu = per_cu_cache[dev].load(std::memory_order_relaxed);
-    if (per_cu == 0) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, stft_mag_forward_persistent_kernel<LOGM>, kThreads, lds) != hipSuccess || per_cu < 1) {
-            (void)hipGetLastError();
-            per_cu = 4;
-        }
-        per_cu_cache[dev].store(per_cu, std::memory_order_relaxed);
-    }
-    const int64_t groups = (work + G::slots - 1) / G::slots, cap = (int64_t)cu_count() * per_cu;
-    hipLaunchKernelGGL(stft_mag_forward_persistent_kernel<LOGM>, dim3((unsigned)(groups < cap ? groups : cap)), dim3(kThreads), lds, st, a);
+    static sot::GridCache cache;   // (one per instantiation, i.e. per kernel; not launch_persistent: the caller reads the launch's status)
+    const int resident = sot::cached_resident_grid(cache, stft_mag_forward_persistent_kernel<LOGM>, kThreads, lds);
+    hipLaunchKernelGGL(stft_mag_forward_persistent_kernel<LOGM>, dim3(sot::persistent_grid((work + G::slots - 1) / G::slots, resident)), dim3(kThreads), lds, st, a);
 }
 
 // Measured (tools/ab_stft.py, 256 clips x 4096 samples): n_fft 2048 forward 25.2 -> 21.9 us, forward of a pair 42.4 -> 38.1 us; n_fft 512
@@ -1386,17 +1360,9 @@ constexpr int64_t kWave2MinFrames = 3072;
 static bool launch_forward_wave2(const StftArgs& a, int64_t frames_total, hipStream_t st)
 {
     if (a.logm != 10 || frames_total < kWave2MinFrames) return false;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {   // idempotent per device; a benign race sets it twice
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mag_forward_wave2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kWave2LdsBytes) != hipSuccess)
-            (void)hipGetLastError();
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
-    const int64_t want = (frames_total + kWave2Waves - 1) / kWave2Waves, cap = cu_count();   // one 1024-thread workgroup per CU
-    hipLaunchKernelGGL(stft_mag_forward_wave2_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kWave2Threads), kWave2LdsBytes, st, a);
+    sot::allow_full_lds_once<stft_mag_forward_wave2_kernel>();
+    const int grid = sot::capped_grid((frames_total + kWave2Waves - 1) / kWave2Waves, 1);   // one 1024-thread workgroup per CU
+    hipLaunchKernelGGL(stft_mag_forward_wave2_kernel, dim3(grid), dim3(kWave2Threads), kWave2LdsBytes, st, a);
     return true;
 }
 
@@ -1409,17 +1375,8 @@ static bool launch_backward_spec_clip(const StftArgs& a, hipStream_t st)
 {
     if (a.logm != 10 || a.spec_in == nullptr || a.frames > kWave2Waves || a.frames < 1 || (a.hop & 1) != 0 || a.batch < kBwdClipMinClips)
         return false;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mag_backward_spec_clipw_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kClipwLdsBytes) != hipSuccess)
-            (void)hipGetLastError();
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
-    const int64_t cap = cu_count();
-    hipLaunchKernelGGL(stft_mag_backward_spec_clipw_kernel, dim3((unsigned)(a.batch < cap ? a.batch : cap)), dim3(kWave2Threads), kClipwLdsBytes, st, a);
+    sot::allow_full_lds_once<stft_mag_backward_spec_clipw_kernel>();
+    hipLaunchKernelGGL(stft_mag_backward_spec_clipw_kernel, dim3(sot::capped_grid(a.batch, 1)), dim3(kWave2Threads), kClipwLdsBytes, st, a);
     return true;
 }
 
@@ -1429,18 +1386,14 @@ static bool launch_backward_spec_wave2(const StftArgs& a, int64_t groups_total, 
     if (a.logm != 10 || groups_total < kBwdWave2MinGroups || (a.hop != 256 && a.hop != 512) ||
         (reinterpret_cast<uintptr_t>(a.partial) & 7u) != 0 || (a.span & 1) != 0)
         return false;
-    void (*kern)(const StftArgs) = a.hop == 256 ? stft_mag_backward_spec_wave2_kernel<2> : stft_mag_backward_spec_wave2_kernel<4>;
-    static bool attr_done[64][2] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    const int which = a.hop == 256 ? 0 : 1;
-    if (dev < 0 || dev >= 64 || !attr_done[dev][which]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBwdWave2LdsBytes) != hipSuccess)
-            (void)hipGetLastError();
-        if (dev >= 0 && dev < 64) attr_done[dev][which] = true;
-    }
-    const int64_t want = (groups_total + kBwdWave2Waves - 1) / kBwdWave2Waves, cap = cu_count();   // one 512-thread workgroup per CU
-    hipLaunchKernelGGL(kern, dim3((unsigned)(want < cap ? want : cap)), dim3(kBwdWave2Threads), kBwdWave2LdsBytes, st, a);
+    const int grid = sot::capped_grid((groups_total + kBwdWave2Waves - 1) / kBwdWave2Waves, 1);   // one 512-thread workgroup per CU
+    auto go = [&](auto frames_tag) {
+        constexpr auto kern = stft_mag_backward_spec_wave2_kernel<decltype(frames_tag)::value>;
+        sot::allow_full_lds_once<kern>();
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kBwdWave2Threads), kBwdWave2LdsBytes, st, a);
+    };
+    if (a.hop == 256) go(std::integral_constant<int, 2>{});
+    else go(std::integral_constant<int, 4>{});
     return true;
 }
 
@@ -1449,17 +1402,9 @@ static bool launch_backward_spec_wave2(const StftArgs& a, int64_t groups_total, 
 static bool launch_forward_wavew(const StftArgs& a, int64_t frames_total, hipStream_t st)
 {
     if (a.logm != 10 || frames_total < kFwdWavewMinFrames || frames_total >= kWave2MinFrames) return false;
-    static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_mag_forward_wavew_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kFwdwLdsBytes) != hipSuccess)
-            (void)hipGetLastError();
-        if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
-    const int64_t want = (frames_total + kFwdwWaves - 1) / kFwdwWaves, cap = 3 * (int64_t)cu_count();   // three 256-thread workgroups per CU (LDS)
-    hipLaunchKernelGGL(stft_mag_forward_wavew_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(kFwdwThreads), kFwdwLdsBytes, st, a);
+    sot::allow_full_lds_once<stft_mag_forward_wavew_kernel>();
+    const int grid = sot::capped_grid((frames_total + kFwdwWaves - 1) / kFwdwWaves, 3);   // three 256-thread workgroups per CU (LDS)
+    hipLaunchKernelGGL(stft_mag_forward_wavew_kernel, dim3(grid), dim3(kFwdwThreads), kFwdwLdsBytes, st, a);
     return true;
 }
 
@@ -1504,7 +1449,7 @@ int sot_stft_mag_forward_spec(const float* audio, int64_t batch, int64_t samples
     (void)hipGetLastError();
     if (!launch_forward_wave(a, batch * a.frames, reinterpret_cast<hipStream_t>(stream)))
         launch_forward(batch * a.frames, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_stft_mag_forward_pair(const float* audio_a, int64_t row_stride_a, const float* audio_b, int64_t row_stride_b,
@@ -1531,7 +1476,7 @@ int sot_stft_mag_forward_pair_spec(const float* audio_a, int64_t row_stride_a, c
     (void)hipGetLastError();
     if (!launch_forward_wave(a, 2 * batch_each * a.frames, reinterpret_cast<hipStream_t>(stream)))
         launch_forward(2 * batch_each * a.frames, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 size_t sot_stft_backward_workspace_bytes(int64_t batch, int64_t samples, int n_fft, int hop)
@@ -1574,14 +1519,14 @@ int sot_stft_mag_backward_spec(const float* audio, const float* spec, int64_t ba
     a.span = (int)span;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     (void)hipGetLastError();
-    if (spec != nullptr && launch_backward_spec_clip(a, st)) return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;   // overlap-add inside
+    if (spec != nullptr && launch_backward_spec_clip(a, st)) return sot::launch_status();   // overlap-add inside
     if (spec != nullptr && launch_backward_spec_wave2(a, batch * a.groups, st)) { /* one wavefront per frame group */ }
     else if (spec != nullptr) SOT_STFT_LAUNCH(stft_mag_backward_spec_kernel, batch * a.groups, sizeof(float) * (size_t)span, st, a);
     else SOT_STFT_LAUNCH(stft_mag_backward_partial_kernel, batch * a.groups, sizeof(float) * (size_t)span, st, a);
-    if (hipGetLastError() != hipSuccess) return SOT_ERR_LAUNCH;
+    if (sot::launch_status() != SOT_OK) return SOT_ERR_LAUNCH;
     const int64_t per_clip = (samples + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(stft_overlap_add_kernel, dim3((unsigned)(per_clip < 64 ? per_clip : 64), (unsigned)(batch < 65535 ? batch : 65535)), dim3(kThreads), 0, st, a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 size_t sot_spec_distance_workspace_bytes(void) { return sizeof(double) * (size_t)sot_stft::kDistBlocks; }
@@ -1602,7 +1547,7 @@ int sot_spec_distance_forward(const float* target, const float* value, int64_t c
     (void)hipGetLastError();
     hipLaunchKernelGGL(spec_distance_partial_kernel, dim3(a.n_partial), dim3(kThreads), 0, st, a);
     hipLaunchKernelGGL(spec_distance_finish_kernel, dim3(1), dim3(kThreads), 0, st, a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_spec_distance_backward(const float* target, const float* value, int64_t count, float mag_weight, float logmag_weight,
@@ -1620,7 +1565,7 @@ int sot_spec_distance_backward(const float* target, const float* value, int64_t 
     const int grid = (int)(need < 256 * 32 ? need : 256 * 32);
     (void)hipGetLastError();
     hipLaunchKernelGGL(spec_distance_backward_kernel, dim3(grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_spec_distance_rows_forward(const float* target, const float* value, int64_t rows, int64_t count_per_row, float mag_weight,
@@ -1634,7 +1579,7 @@ int sot_spec_distance_rows_forward(const float* target, const float* value, int6
     a.l2 = l2; a.out = out; a.accumulate = accumulate;
     (void)hipGetLastError();
     hipLaunchKernelGGL(spec_distance_rows_kernel, dim3((unsigned)rows), dim3(kRowDistThreads), 0, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 int sot_spec_distance_rows_backward(const float* target, const float* value, int64_t rows, int64_t count_per_row, float mag_weight,
@@ -1652,7 +1597,7 @@ int sot_spec_distance_rows_backward(const float* target, const float* value, int
     const int grid = (int)(need < 256 * 32 ? need : 256 * 32);
     (void)hipGetLastError();
     hipLaunchKernelGGL(spec_distance_rows_backward_kernel, dim3(grid), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), a, rows);
-    return hipGetLastError() == hipSuccess ? SOT_OK : SOT_ERR_LAUNCH;
+    return sot::launch_status();
 }
 
 }  // extern "C"

@@ -499,3 +499,85 @@ def test_one_long_side_takes_the_torch_route_instead_of_raising():
         got = Wasserstein1D(p=1)(x, y, x_pos=px, y_pos=py)
     want = Wasserstein1D(p=1)(x.cpu(), y.cpu(), x_pos=px.cpu(), y_pos=py.cpu())
     torch.testing.assert_close(got.cpu(), want, rtol=1e-5, atol=0)
+
+
+# the child of test_first_use_from_several_threads: argv[1] is the repository root
+_FIRST_USE_CHILD = r'''
+import sys, threading
+sys.path.insert(0, sys.argv[1])
+import torch
+import sot_amd
+from sot_amd import _native as nat, spectra
+
+nat.load(build_if_missing=False)
+dev = torch.device("cuda:0")
+g = torch.Generator().manual_seed(11)
+rand = lambda *shape: torch.rand(*shape, generator=g)
+clips32, clips64 = (rand(32, 4096) - 0.5).to(dev), (rand(64, 4096) - 0.5).to(dev)
+grad_mag = rand(64, 16, 1025).to(dev)
+target, value = (rand(4, 4096) - 0.5).to(dev), (rand(4, 4096) - 0.5).to(dev)
+keys = rand(8, 2048).to(dev)
+amp, f0, grad_audio = rand(4, 16, 8).to(dev), (100.0 + 300.0 * rand(4, 16, 1)).to(dev), (rand(4, 4096) - 0.5).to(dev)
+sizes = (2048, 1024, 512, 256, 128, 64)
+hann = [torch.hann_window(s, periodic=True, device=dev) for s in sizes]
+torch.cuda.synchronize()
+
+
+def routes():
+    out = {}
+    out["stft forward (one wave per frame)"] = spectra.stft_magnitude(clips32, 2048, 256)
+    _, spec = nat.stft_mag_forward(clips64, hann[0], 2048, 256, want_spec=True)
+    out["stft backward from the spectrum (per clip)"] = nat.stft_mag_backward(clips64, hann[0], 2048, 256, grad_mag, spec=spec)
+    out["mss loss"], out["mss gradient"] = nat.mss_loss_and_grad(target, value, sizes, hann, 1.0, 0.0)
+    out["sorted keys"], out["sort indices"] = nat.segmented_sort(keys)
+    a, f = amp.clone().requires_grad_(True), f0.clone().requires_grad_(True)
+    spectra.sinusoidal_synth(a, f, 4096).backward(grad_audio)
+    out["synth amplitude gradient"], out["synth frequency gradient"] = a.grad, f.grad
+    return out
+
+
+N = 4
+start, results, errors = threading.Barrier(N), [None] * N, []
+
+
+def work(i):
+    try:
+        stream = torch.cuda.Stream(dev)
+        with torch.cuda.stream(stream):
+            start.wait()
+            results[i] = routes()
+        stream.synchronize()
+    except BaseException as e:   # reported by the main thread
+        errors.append(repr(e))
+        start.abort()
+
+
+threads = [threading.Thread(target=work, args=(i,)) for i in range(N)]
+for t in threads:
+    t.start()
+for t in threads:
+    t.join()
+torch.cuda.synchronize()
+assert not errors, errors
+want = routes()
+torch.cuda.synchronize()
+bad = [f"thread {i}: {name}" for i, got in enumerate(results) for name in want if not torch.equal(got[name], want[name])]
+assert not bad, bad
+print("first use from %d threads: %d results each, all equal to the sequential ones" % (N, len(want)))
+'''
+
+
+def test_first_use_from_several_threads():
+    """The host launch layer (csrc/sot_host.hpp) under its hardest use: in a fresh process, 4 threads on 4 streams make the process's FIRST
+    calls of the routes that opt a kernel in to the full LDS and size a grid by the CU count -- STFT forward (512 frames: one wave per frame)
+    and backward from the stored spectrum (64 clips: the per-clip kernel), MSSLoss with the six paper sizes, the segmented sort, the
+    synthesiser's backward -- all at once.  Every one of these calls is deterministic (test_stft_producer, test_mss_fused, test_row_loop_gpu
+    and test_oscillator_bank assert two runs bit-identical), so each thread's results equal those of the same calls made afterwards on one thread, bit for bit."""
+    import os
+    import subprocess
+    import sys
+    native()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, "-c", _FIRST_USE_CHILD, root], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    assert "all equal to the sequential ones" in res.stdout

@@ -1,6 +1,6 @@
 """-m gpu: the SECOND AND LATER ROWS of a workgroup, on every route of the row kernels.
 
-Every row kernel is persistent: launch_persistent (csrc/sot_launch.hpp) starts min(row groups, resident workgroups) workgroups and each
+Every row kernel is persistent: launch_persistent (csrc/sot_host.hpp) starts min(row groups, resident workgroups) workgroups and each
 walks rows w, w + grid, w + 2 grid, ... through the same LDS regions.  A loop-carried error -- stale LDS of the previous row, a missing
 barrier between two rows, a partial last row group in the wrong barrier -- shows from a workgroup's second row on, and the other tests
 reach that row only by the grace of an occupancy figure nobody asserts.  Here the batch forces it:
@@ -104,12 +104,12 @@ CASES = [
     C("gen300x411", "fwd", 300, 64, 4, PICK + " (64, 8), n != m", m=411, flags=NS),
     # ---- per-row positions: the pre-sort kernel (launch_rowpos_sort: one wave per array, 2 B arrays; it loops too: 2 B > 3 * 32 CUs except at
     #      2048 points, where 2 B = 12294 arrays guarantee its second round and, by the launch's own cap of 16 waves per CU, the third) + RP kernels ----
-    C("rp512", "fwd", 512, 64, 4, HIP + ":507 full_rp -> dispatch_forward_full_rowpos_g<64>; " + HIP + ":384 launch_rowpos_sort", rowpos=True),
-    C("rp1024", "fwd", 1024, 128, 2, HIP + ":507 -> dispatch_forward_full_rowpos_g<128>", rowpos=True),
-    C("rp2048", "fwd", 2048, 256, 1, HIP + ":507 -> dispatch_forward_full_rowpos_g<256>", rowpos=True),
-    C("rp700_generic", "fwd", 700, 128, 2, HIP + ":515 dispatch_forward<true>, " + PICK + " (128, 12)", rowpos=True),
-    C("rp2048_stored_perm", "fwd_perm", 2048, 256, 1, HIP + ":448-460 row_perm_out, then row_perm_in", rowpos=True),
-    C("rp700_stored_perm", "fwd_perm", 700, 128, 2, HIP + ":448-460 on the generic gathering kernel", rowpos=True),
+    C("rp512", "fwd", 512, 64, 4, HIP + ":506 full_rp -> dispatch_forward_full_rowpos_g<64>; " + HIP + ":384 launch_rowpos_sort", rowpos=True),
+    C("rp1024", "fwd", 1024, 128, 2, HIP + ":506 -> dispatch_forward_full_rowpos_g<128>", rowpos=True),
+    C("rp2048", "fwd", 2048, 256, 1, HIP + ":506 -> dispatch_forward_full_rowpos_g<256>", rowpos=True),
+    C("rp700_generic", "fwd", 700, 128, 2, HIP + ":514 dispatch_forward<true>, " + PICK + " (128, 12)", rowpos=True),
+    C("rp2048_stored_perm", "fwd_perm", 2048, 256, 1, HIP + ":447-459 row_perm_out, then row_perm_in", rowpos=True),
+    C("rp700_stored_perm", "fwd_perm", 700, 128, 2, HIP + ":447-459 on the generic gathering kernel", rowpos=True),
     # ---- backward: both gradients / y only ----
     C("bwd512", "bwd", 512, 64, 4, BWD + ":31 dispatch_backward_full_g<64, 8, 4>"),
     C("bwd1024", "bwd", 1024, 128, 2, BWD + ":34 <128, 8, 2, 0, 1>; y only :33 the slim layout dispatch_backward_full_y<128, 8, 2, 0, true, 1>"),
@@ -129,15 +129,15 @@ CASES = [
     C("bwd_gen1800", "bwd", 1800, 256, 1, PICK + " (256, 8)", flags=NS),
     C("bwd_gen2100", "bwd", 2100, 1024, 1, PICK + " (1024, 8): the smallest length of the geometry in round figures (see the note below CASES)", flags=NS),
     C("bwd_gen300x411", "bwd", 300, 64, 4, PICK + " (64, 8), n != m", m=411, flags=NS),
-    C("bwd_rp512", "bwd", 512, 64, 4, HIP + ":541 full_rp -> dispatch_backward_full_rowpos_g<64>", rowpos=True),
-    C("bwd_rp2048", "bwd", 2048, 256, 1, HIP + ":541 -> dispatch_backward_full_rowpos_g<256>", rowpos=True),
-    C("bwd_rp700_generic", "bwd", 700, 128, 2, HIP + ":557 dispatch_backward<true>, " + PICK + " (128, 12)", rowpos=True),
+    C("bwd_rp512", "bwd", 512, 64, 4, HIP + ":540 full_rp -> dispatch_backward_full_rowpos_g<64>", rowpos=True),
+    C("bwd_rp2048", "bwd", 2048, 256, 1, HIP + ":540 -> dispatch_backward_full_rowpos_g<256>", rowpos=True),
+    C("bwd_rp700_generic", "bwd", 700, 128, 2, HIP + ":556 dispatch_backward<true>, " + PICK + " (128, 12)", rowpos=True),
     # ---- training form (row losses + d mean / d y from one pass) and the merge-free training form ----
-    C("train512", "train", 512, 64, 4, HIP + ":543 row losses from the y-only kernel; " + BWD + ":31"),
-    C("train2048", "train", 2048, 256, 1, HIP + ":543; " + BWD + ":36"),
-    C("train1025", "train", 1025, 128, 2, HIP + ":543; " + BWD + ":52"),
-    C("tiefree2048", "tiefree", 2048, 256, 1, HIP + ":551 area -> " + BWD + ":13 dispatch_area_train_g<256, 8, 1>"),
-    C("tiefree1025", "tiefree", 1025, 128, 2, HIP + ":551 -> " + BWD + ":18 dispatch_area_train_g<128, 9, 2, 1025>"),
+    C("train512", "train", 512, 64, 4, HIP + ":542 row losses from the y-only kernel; " + BWD + ":31"),
+    C("train2048", "train", 2048, 256, 1, HIP + ":542; " + BWD + ":36"),
+    C("train1025", "train", 1025, 128, 2, HIP + ":542; " + BWD + ":52"),
+    C("tiefree2048", "tiefree", 2048, 256, 1, HIP + ":550 area -> " + BWD + ":13 dispatch_area_train_g<256, 8, 1>"),
+    C("tiefree1025", "tiefree", 1025, 128, 2, HIP + ":550 -> " + BWD + ":18 dispatch_area_train_g<128, 9, 2, 1025>"),
     # ---- position gradients: one shared and one per-row case per generic geometry whose gradient layout fits the LDS ((1024, 16) does not) ----
     C("posgrad300", "posgrad", 300, 64, 4, "csrc/sot_posgrad.hip:202 setup_launch, " + PICK + " (64, 8)"),
     #      (the longer side picks the geometry; the other side is short because chance ties between the two sides' levels grow with n m / 2^24)
@@ -149,7 +149,7 @@ CASES = [
     C("posgrad_rp1600x100", "posgrad", 1600, 256, 1, PICK + " (256, 8), per-row positions", m=100, rowpos=True),
     C("posgrad_rp2100x90", "posgrad", 2100, 1024, 1, PICK + " (1024, 8), per-row positions", m=90, rowpos=True),
     # ---- quantile tensors and their gradients: n + m <= 600 keeps the [B, n + m] outputs small, which leaves the geometries (64, 8) and (128, 12) ----
-    C("quant300", "quant", 300, 64, 4, HIP + ":665 run_forward(quant), " + PICK + " (64, 8)"),
+    C("quant300", "quant", 300, 64, 4, HIP + ":667 run_forward(quant), " + PICK + " (64, 8)"),
     C("quant520x80", "quant", 520, 128, 2, PICK + " (128, 12)", m=80),
     C("quant_rp300", "quant", 300, 64, 4, PICK + " (64, 8), per-row positions", rowpos=True),
     C("quant_rp520x80", "quant", 520, 128, 2, PICK + " (128, 12), per-row positions", m=80, rowpos=True),
@@ -161,12 +161,12 @@ CASES = [
     C("csr64", "csr", 64, 64, 4, "csrc/sot_csr.hip:39 " + PICK + " (64, 8) of (max_n, max_m)"),
     C("csr500", "csr", 500, 64, 4, "csrc/sot_csr.hip:39 " + PICK + " (64, 8)"),
     # ---- segmented sort: one wave per row (sot_segmented_sort: n <= 2048), i.e. R = 32 CUs rows ----
-    C("sort100", "sort", 100, 64, 4, HIP + ":768 launch_segmented_sort_wave<2>"),
-    C("sort512", "sort", 512, 64, 4, HIP + ":769 launch_segmented_sort_wave<8>"),
-    C("sort2048", "sort", 2048, 64, 4, HIP + ":771 launch_segmented_sort_wave<32>"),
+    C("sort100", "sort", 100, 64, 4, HIP + ":770 launch_segmented_sort_wave<2>"),
+    C("sort512", "sort", 512, 64, 4, HIP + ":771 launch_segmented_sort_wave<8>"),
+    C("sort2048", "sort", 2048, 64, 4, HIP + ":773 launch_segmented_sort_wave<32>"),
     # ---- the batch mean in the row kernel's last workgroup ----
-    C("fused2048", "fused", 2048, 256, 1, HIP + ":497 mean_tail; " + FWD + ":13 / :68"),
-    C("fused513", "fused", 513, 64, 4, HIP + ":497 mean_tail; " + FWD + ":21 / :81"),
+    C("fused2048", "fused", 2048, 256, 1, HIP + ":496 mean_tail; " + FWD + ":13 / :68"),
+    C("fused513", "fused", 513, 64, 4, HIP + ":496 mean_tail; " + FWD + ":21 / :81"),
 ]
 # Lengths the issue leaves open are the smallest that reach the kernel or geometry (just past the previous geometry's capacity, no multiple of
 # the tile).  The generic backward on (1024, 8) first ran at 5000 points as the forward does: paper mode's d / d y came out at 1.065e-5 of the
