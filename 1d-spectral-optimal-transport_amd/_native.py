@@ -31,7 +31,7 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 17                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 18                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
 FIR_TILE = 1024                  # include/sot_hip.h: SOT_FIR_TILE (outputs per workgroup of the FIR kernel)
 FIR_MIN_TAPS, FIR_MAX_TAPS, FIR_MAX_SAMPLES = 3, 512, 1 << 20   # the FIR kernels' domain (include/sot_hip.h: sot_fir_same_forward)
@@ -418,10 +418,14 @@ def _want_tail(fused_mean):
 
 def _needs_workspace(pr: SotProblem, flags, plan) -> bool:
     """Shared positions that still have to be planned; or per-row positions nobody has sorted (no row_perm_in / row_perm_out): the
-    library's pre-sort kernel leaves the rows' permutations in the workspace (optional there -- without it the row kernel sorts in LDS)."""
+    library's pre-sort kernel leaves the rows' permutations in the workspace (optional there -- without it the row kernel sorts in LDS),
+    where that kernel runs (csrc/sot_launch.hpp: rowpos_presort_runs -- elsewhere sot_workspace_bytes is 0 and nothing is allocated)."""
     if not (flags & FLAG_REQUIRE_SORT) or plan is not None:
         return False
-    return pr.xpos_row_stride == 0 or (not pr.row_perm_in and not pr.row_perm_out)
+    if pr.xpos_row_stride == 0:
+        return True
+    return (not pr.row_perm_in and not pr.row_perm_out and pr.B > 0 and 2 <= pr.n <= 2048 and 2 <= pr.m <= 2048
+            and not (flags & FLAG_NO_SPECIALIZE))
 
 
 def workspace(pr: SotProblem, device) -> torch.Tensor:

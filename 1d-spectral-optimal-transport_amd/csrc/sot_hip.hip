@@ -448,8 +448,8 @@ int setup_launch(const sot_problem* pr, bool with_grad, void* workspace, size_t 
     // per-row positions nobody has sorted yet: the wave-sort kernel runs first (round 6) and the row kernel gathers through its
     // permutations -- into the caller's row_perm_out, else into the workspace when it is large enough (sot_workspace_bytes), else the
     // row kernel sorts in LDS as before
-    if (l.rowpos && (pr->flags & SOT_FLAG_REQUIRE_SORT) && a.perm_in == nullptr && pr->B > 0 && n >= 2 && m >= 2 && n <= 2048 &&
-        m <= 2048 && !(pr->flags & SOT_FLAG_NO_SPECIALIZE)) {
+    // (the domain is rowpos_presort_runs, csrc/sot_launch.hpp: the predicate sot_workspace_bytes reports room by)
+    if (rowpos_presort_runs(pr)) {
         uint16_t* dest = pr->row_perm_out;
         if (dest == nullptr && workspace != nullptr && workspace_bytes >= rowpos_perm_bytes(pr->B, n, m)) dest = reinterpret_cast<uint16_t*>(workspace);
         if (dest != nullptr) {
@@ -629,7 +629,7 @@ size_t sot_workspace_bytes(const sot_problem* prob)
 {
     if (prob == nullptr || prob->n < 1 || prob->m < 1) return 0;
     if (prob->xpos_row_stride != 0)   // per-row positions: room for the pre-sort's permutations (optional: without it the row kernel sorts in LDS)
-        return (prob->flags & SOT_FLAG_REQUIRE_SORT) && prob->row_perm_in == nullptr && prob->row_perm_out == nullptr && prob->B > 0
+        return sot::rowpos_presort_runs(prob) && prob->row_perm_out == nullptr   // 0 where the pre-sort cannot run (setup_launch's own predicate)
                    ? sot::rowpos_perm_bytes(prob->B, prob->n, prob->m) : 0;
     return sot::ws_layout(prob->n, prob->m).total;
 }

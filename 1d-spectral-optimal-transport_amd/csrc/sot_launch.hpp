@@ -50,6 +50,14 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 struct WsLayout { size_t sx, sy, px, py, ident, total; };
 // the permutation image of a per-row-position call (setup_launch: the pre-sort kernel's output when the caller passes no row_perm_out)
 static inline size_t rowpos_perm_bytes(int64_t B, int n, int m) { return align_up((size_t)B * ((size_t)n + (size_t)m) * sizeof(uint16_t), 256); }
+// The pre-sort kernel's domain: per-row positions that a call has to sort itself (no row_perm_in), rows of 2 ... 2048 points, kernels with the
+// length at compile time allowed.  ONE predicate for setup_launch, which runs the pre-sort, and for sot_workspace_bytes, which reports room for
+// its image only where it can run (mirrored in the binding's _native._needs_workspace).
+static inline bool rowpos_presort_runs(const sot_problem* pr)
+{
+    return pr->xpos_row_stride != 0 && (pr->flags & SOT_FLAG_REQUIRE_SORT) && pr->row_perm_in == nullptr && pr->B > 0 && pr->n >= 2 && pr->m >= 2 &&
+           pr->n <= 2048 && pr->m <= 2048 && !(pr->flags & SOT_FLAG_NO_SPECIALIZE);
+}
 
 static inline WsLayout ws_layout(int n, int m)
 {
@@ -80,6 +88,8 @@ static inline void launch_maybe_profiled(Kernel kern, int grid, int block, size_
 // launch_persistent (sot_host.hpp) for the full-row kernels: the launch goes through launch_maybe_profiled, i.e. it consumes an armed
 // sot_profile_next_launch.
 // A workgroup's second and later rows are tested in tests/test_row_loop_gpu.py, on batches that force them; a new row kernel adds a line to its CASES.
+// What a call may write and read (outputs, workspace, row gaps) is tested in tests/test_memory_contract_gpu.py; a new row kernel or entry point
+// adds a line to that file's CASES too.
 template <auto Kern, class Args>
 static inline hipError_t launch_persistent_profiled(const Args& args, size_t lds, int64_t want, int block, hipStream_t s)
 {

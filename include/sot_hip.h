@@ -15,7 +15,12 @@
  *     no allocation, no host synchronisation, graph-capturable;
  *   - return value: SOT_OK (0) or a negative sot_status; nothing aborts, nothing is
  *     enqueued when an error is returned;
- *   - rows are independent: a caller shards a batch by passing a sub-range of rows.
+ *   - rows are independent: a caller shards a batch by passing a sub-range of rows;
+ *   - memory: a call writes only the elements of its outputs and the first *_workspace_bytes() bytes of its workspace; it reads
+ *     nothing outside its rows whose value can reach a result (the gaps between strided rows and whatever surrounds a buffer may
+ *     hold anything, NaN included); it leaves its inputs unchanged.  Alignment: every buffer needs the alignment of its element
+ *     type and no more unless stated with the buffer; a better-aligned call may take a faster kernel, a worse-aligned one is still
+ *     correct.  tests/test_memory_contract_gpu.py holds every entry point to this with guard bands around each buffer.
  */
 #ifndef SOT_HIP_H
 #define SOT_HIP_H
@@ -27,9 +32,10 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 17   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+#define SOT_ABI_VERSION 18   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
                               * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
-                              *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics; 17: sot_w1d_mixed_*) */
+                              *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics; 17: sot_w1d_mixed_*;
+                              *  18: sot_workspace_bytes is 0 for per-row positions outside the pre-sort's domain) */
 
 typedef enum sot_status {
     SOT_OK = 0,
@@ -67,7 +73,11 @@ typedef enum sot_status {
                                       to autograd, so a run of equal levels hands its whole gradient to one member).  With it, p == 1
                                       with SOT_FLAG_SAME_GRID and no cutoff gets a MERGE-FREE training form (gradient w.r.t. y alone):
                                       8192 x 2048 rows 72.7 -> 47.5 us, 16384 x 1025 rows 76 -> 69 us.  Gradient entries of rows without tied
-                                      levels are unchanged; the loss value is the merge-free forward kernel's (<= 3e-7 from the merge walk's) */
+                                      levels are unchanged; the loss value is the merge-free forward kernel's (<= 3e-7 from the merge walk's).
+                                      The flag is a PERMISSION: the merge-free form serves the row lengths with a compile-time training kernel, and for
+                                      the power-of-two lengths (512 ... 4096) only when the rows of x, y and grad_y start on 16-byte boundaries (row
+                                      strides multiples of 4); any other call -- another length, rows 4 bytes off -- returns the reference's tie order
+                                      on tied rows, as without the flag.  129, 257, 513, 1025 and 2049 bins are served at every alignment */
 
 /* One batch of spectrum pairs.  Mirrors the arguments of Wasserstein1D.forward
  * (losses.py:129) after its [batch,time,N] -> [B,N] reshape (losses.py:157-170). */
@@ -98,7 +108,10 @@ typedef struct sot_problem {
      * Round 6: rows of 2 ... 2048 positions are sorted AHEAD of the row kernel by a kernel of their own (one wavefront per row, a packed-word
      * network in registers: csrc/sot_wave_sort.hpp) whenever there is a place for the permutations -- row_perm_out, else the call's workspace
      * when it holds sot_workspace_bytes() bytes, else the row kernel sorts in LDS as before.  Either way an image that a call has written holds
-     * the stable sort permutations of every row. */
+     * the stable sort permutations of every row.
+     * Alignment of the image (row_perm_out, row_perm_in, or the workspace standing in for it): 2 bytes are enough.  On a 16-byte boundary, with
+     * n == m in {512, 1024, 2048} and 16-byte aligned weight rows, the calls take the compile-time-length kernels; on an 8-byte boundary with
+     * n, m multiples of 4 and 16-byte aligned position rows the pre-sort stores packed words; anything less runs the element-wise forms. */
     uint16_t *row_perm_out;
     const uint16_t *row_perm_in;
 } sot_problem;
@@ -109,7 +122,8 @@ const char *sot_status_string(int status);
 /* Bytes of device workspace the calls below need for this problem (host-side arithmetic only).  Shared positions with
  * SOT_FLAG_REQUIRE_SORT and no plan: required.  Per-row positions with SOT_FLAG_REQUIRE_SORT and neither row_perm_in nor row_perm_out
  * (round 6): room for the pre-sort's [B, n + m] uint16 permutations -- OPTIONAL: a call with a smaller (or no) workspace sorts inside the
- * row kernel.  0 otherwise. */
+ * row kernel -- and only where the pre-sort runs (ABI 18): 2 <= n, m <= 2048 and no SOT_FLAG_NO_SPECIALIZE; any other per-row problem
+ * sorts in the row kernel and uses no workspace.  0 otherwise, and for prob == NULL, n < 1 or m < 1. */
 size_t sot_workspace_bytes(const sot_problem *prob);
 
 /*
@@ -148,7 +162,7 @@ int sot_w1d_forward(const sot_problem *prob, float *row_loss /* [B] */,
  * accumulation: *mean_out = (float)(sum_r row_loss[r] / denom) and, if sum_out != NULL,
  * *sum_out = sum_r row_loss[r] (the per-shard partial that is all-reduced across GPUs).
  * hinge_threshold: rows are replaced by relu(row - threshold) first when apply_hinge != 0
- * (losses.py:203-205).
+ * (losses.py:203-205).  B == 0 is a defined call (the sum of no rows: *mean_out = 0 / denom); B < 0: SOT_ERR_BAD_SHAPE.
  */
 int sot_w1d_reduce_mean(const float *row_loss, int64_t B, double denom, int apply_hinge, float hinge_threshold,
                         float *mean_out, double *sum_out, void *stream);
@@ -174,7 +188,7 @@ int sot_w1d_backward(const sot_problem *prob,
  * over the rows (the backward kernel's merge walk also accumulates the loss, bit-identical to sot_w1d_forward) followed by
  * the reduction kernel; otherwise forward, backward and reduction are enqueued back to back.  No hinge (the hinge changes
  * which rows receive a gradient).  A caller whose upstream gradient turns out not to be 1 rescales with sot_scale_inplace.
- * completion_counters: see sot_w1d_loss.
+ * completion_counters: see sot_w1d_loss.  B == 0: SOT_ERR_BAD_SHAPE (the mean of no rows is undefined), nothing is touched.
  */
 int sot_w1d_loss_and_grad(const sot_problem *prob, float *row_loss /* [B] */, double denom, float *mean_out, double *sum_out,
                           float grad_scale, float *grad_y /* [B,m] */, uint32_t *completion_counters /* or NULL */,
@@ -206,6 +220,7 @@ int sot_scale_inplace(float *data, int64_t count, const float *scalar, void *str
  *     trip at its end and the last one an agent-scope acquire plus a re-read of the row losses, which together cost more
  *     than the ~2.6 us kernel boundary + mean kernel they replace; the shipped Python binding therefore passes NULL unless
  *     asked.
+ * B == 0: SOT_ERR_BAD_SHAPE (the mean of no rows is undefined), nothing is touched.
  */
 #define SOT_COMPLETION_COUNTER_WORDS 16
 int sot_w1d_loss(const sot_problem *prob, float *row_loss /* [B] */, double denom, int apply_hinge,
@@ -307,7 +322,7 @@ int sot_w1d_mixed_backward(const sot_problem *prob, const float *grad_row, int64
 int sot_w1d_mixed_position_grad(const sot_problem *prob, const float *grad_row, int64_t grad_row_stride, float grad_scale,
                                 float *grad_pos /* [B,K]: the per-row side */, void *workspace, size_t workspace_bytes, void *stream);
 
-/* out[c] = sum_r rows[r * row_stride + c], c < n, in a fixed order with fp64 accumulation. */
+/* out[c] = sum_r rows[r * row_stride + c], c < n, in a fixed order with fp64 accumulation (B == 0: zeros). */
 int sot_column_sum(const float *rows, int64_t B, int32_t n, int64_t row_stride, float *out /* [n] */, void *stream);
 
 /*
