@@ -21,6 +21,10 @@ import torch
 
 from . import _native as nat
 from . import _torch_path as tp
+from . import ops as _ops_module  # noqa: F401 -- registers the sot_amd:: custom ops
+
+_o = torch.ops.sot_amd                      # the route of a call that torch.compile / torch.export is tracing (ops.py); eager never takes it
+_compiling = torch.compiler.is_compiling
 
 # (wasserstein_1d_csr -- ragged supports in CSR form -- is retired from the public surface since round 4: zero-masked dense rows are
 #  config 4; the function itself stays for its tests and the C entry point)
@@ -174,7 +178,7 @@ def _is_shared_row(t) -> bool:
     if t.ndim == 1:
         return True
     lead = [(size, stride) for size, stride in zip(t.shape[:-1], t.stride()[:-1]) if size > 1]
-    return bool(lead) and all(stride == 0 for _, stride in lead)
+    return len(lead) > 0 and all(stride == 0 for _, stride in lead)   # (len(): Dynamo does not trace bool() of a list)
 
 
 def mixed_route_applies(x, y, xpos, ypos, return_quantiles=False) -> bool:
@@ -251,6 +255,8 @@ def _mixed_row_losses(x, y, xpos, ypos, p, flags, plans):
     planned once per tensor version, as on the all-shared route)."""
     x, y, xpos, ypos = _marshal_mixed(x, y, xpos, ypos)
     grid = xpos if xpos.ndim == 1 else ypos
+    if _compiling():
+        return _o.w1d_rows(x, y, xpos, ypos, float(p), flags)
     plan = plans.get(grid, grid) if (flags & nat.FLAG_REQUIRE_SORT) else None
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)):
         return _MixedRowLoss.apply(x, y, xpos, ypos, float(p), flags, plan)
@@ -287,6 +293,8 @@ class _Quantiles(torch.autograd.Function):
 
 def _quantile_tensors(x, y, xpos, ypos, p, flags, plan):
     """return_quantiles on the HIP route: through autograd when a gradient can be asked for, the plain native call otherwise."""
+    if _compiling():
+        return _o.w1d_quantiles(x, y, xpos, ypos, p, flags)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)):
         return _Quantiles.apply(x, y, xpos, ypos, p, flags, plan)
     return nat.quantiles(x, y, xpos, ypos, p, flags, plan)
@@ -430,9 +438,11 @@ def wasserstein_1d(u_values, v_values, u_weights=None, v_weights=None, p=1, requ
     upos, vpos = shared_row(u_values), shared_row(v_values)
     x, y, upos, vpos = _prepare(u_weights, v_weights, upos, vpos)
     flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
-    plan = _functional_plans.get(upos, vpos) if (require_sort and upos.ndim == 1) else None
+    plan = _functional_plans.get(upos, vpos) if (require_sort and upos.ndim == 1 and not _compiling()) else None
     if return_quantiles:
         return _quantile_tensors(x, y, upos, vpos, float(p), flags, plan)
+    if _compiling():
+        return _o.w1d_rows(x, y, upos, vpos, float(p), flags)
     return _RowLoss.apply(x, y, upos, vpos, float(p), flags, plan)
 
 
@@ -571,7 +581,7 @@ class Wasserstein1D(torch.nn.Module):
 
         flags = self._flag_word(kwargs)
         x, y, x_pos_, y_pos_ = _prepare(x, y, x_pos_, y_pos_, checked=True)
-        plan = self._plans.get(x_pos_, y_pos_) if (self.require_sort and x_pos_.ndim == 1) else None
+        plan = self._plans.get(x_pos_, y_pos_) if (self.require_sort and x_pos_.ndim == 1 and not _compiling()) else None   # traced: the op plans
         return x, y, x_pos_, y_pos_, flags, plan, original_shape
 
     def _torch_forward(self, x, y, x_pos_, y_pos_, kwargs, rows_only=False):
@@ -594,7 +604,9 @@ class Wasserstein1D(torch.nn.Module):
             loss = _mixed_row_losses(x, y, x_pos_, y_pos_, self.p, self._flag_word(kwargs), self._plans)
         else:
             x, y, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
-            if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, x_pos_, y_pos_)):
+            if _compiling():
+                loss = _o.w1d_rows(x, y, x_pos_, y_pos_, float(self.p), flags)
+            elif torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, x_pos_, y_pos_)):
                 loss = _RowLoss.apply(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
             else:
                 loss = nat.forward_rows(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
@@ -611,7 +623,7 @@ class Wasserstein1D(torch.nn.Module):
         # fixed_x buffer), no call keywords, float32 GPU rows -> straight into the C++ host path with the cached plan and flag word.
         # Everything the general path below would re-derive per call (domain check, reshapes of positions, flags, plan lookup) was
         # derived when the entry was made; the C++ side checks the weight tensors themselves.
-        hot = self._hot
+        hot = None if _compiling() else self._hot
         if (hot is not None and EARLY_GRADIENT and not kwargs and x.dtype is torch.float32 and y.dtype is torch.float32 and x.is_cuda
                 and y.is_cuda):
             xp = self.fixed_x if x_pos is None else x_pos
@@ -655,6 +667,10 @@ class Wasserstein1D(torch.nn.Module):
             # default reduction: forward and the mean over every row (losses.py:211) in one native call
             x2, y2, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
             grad_on = torch.is_grad_enabled()
+            if _compiling():   # the same two native calls as below, as ops: the training form when only y (and positions) ask for a gradient
+                if grad_on and EARLY_GRADIENT and y2.requires_grad and not x2.requires_grad:
+                    return _o.w1d_mean_and_grad(x2, y2, x_pos_, y_pos_, float(self.p), flags)[0]
+                return _o.w1d_mean(x2, y2, x_pos_, y_pos_, float(self.p), flags)
             glue = nat.glue() if (plan is not None and EARLY_GRADIENT) else None
             if glue is not None and not (grad_on and (x2.requires_grad or x_pos_.requires_grad or y_pos_.requires_grad)):
                 # the hot call (trainer.py:220-228: gradient for the estimate's spectrum only; metrics.py:148: none): C++ host path
@@ -675,7 +691,7 @@ class Wasserstein1D(torch.nn.Module):
             return nat.loss_fused(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)[0]
         loss = self.row_losses(x, y, x_pos, y_pos, **kwargs)
         if dims is None:
-            return _RowMean.apply(loss)  # torch.mean over every row -> 0-d tensor (losses.py:211)
+            return _o.row_mean(loss) if _compiling() else _RowMean.apply(loss)  # torch.mean over every row -> 0-d tensor (losses.py:211)
         loss = loss.reshape(original_shape)
         return torch.mean(loss, dim=dims)
 
@@ -798,6 +814,9 @@ class MSSLoss(torch.nn.Module):
         if native_ok and MSS_FUSED and len(self.fft_sizes) <= 8 and all(int(s) in nat.MSS_FUSED_SIZES for s in self.fft_sizes) and \
                 not (torch.is_grad_enabled() and target_audio.requires_grad):
             sizes = tuple(int(s) for s in self.fft_sizes)
+            if _compiling():
+                return _o.mss_loss(target_audio.float(), audio.float(), list(sizes), float(self.mag_weight), float(self.logmag_weight), kind == "L2",
+                                   per_item, 1.0, torch.is_grad_enabled() and audio.requires_grad)[0]
             # rows the kernels can address: an expanded target (row stride 0) or an overlapping view is copied, as the reference's ops would
             target_audio, audio = nat.rows_view(target_audio), nat.rows_view(audio)
             glue = nat.glue() if (audio.dtype == torch.float32 and target_audio.dtype == torch.float32 and audio.stride(1) == 1 and
@@ -807,7 +826,7 @@ class MSSLoss(torch.nn.Module):
                 return glue.mss_loss(target_audio, audio, wins, list(sizes), float(self.mag_weight), float(self.logmag_weight), kind == "L2", per_item)
             return _MultiScaleSpectralFused.apply(target_audio.float(), audio.float(), sizes, float(self.mag_weight),
                                                   float(self.logmag_weight), kind == "L2", per_item)
-        if native_ok:
+        if native_ok and not _compiling():   # (traced: the composition below, whose transforms are the HIP STFT op)
             return _MultiScaleSpectral.apply(target_audio.float(), audio.float(), self.fft_sizes, float(self.mag_weight),
                                              float(self.logmag_weight), kind == "L2", per_item)
         loss = 0.0
@@ -866,7 +885,10 @@ class Wasserstein1DWithTransform(torch.nn.Module):
         spec_y = spectra.stft_magnitude(y, self.n_fft, self.hop, self.window)
         if self.log:
             spec_x, spec_y = _safe_log(spec_x), _safe_log(spec_y)
-        pos = spectra.unit_frequencies(self.n_fft, float(self.sr), x.device)
+        if _compiling() and x.is_cuda:
+            pos = _o.unit_frequencies(x.detach(), self.n_fft, float(self.sr))
+        else:
+            pos = spectra.unit_frequencies(self.n_fft, float(self.sr), x.device)
         return self.wasserstein(spec_x, spec_y, x_pos=pos, y_pos=pos.clone(), **kwargs)
 
 

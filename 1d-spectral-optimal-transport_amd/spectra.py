@@ -18,6 +18,18 @@ from __future__ import annotations
 
 import torch
 
+_compiling = torch.compiler.is_compiling
+
+
+def _traced_ops():
+    """The sot_amd:: custom ops (ops.py): the GPU route of a call that torch.compile / torch.export is tracing.  Eager calls never ask."""
+    from . import ops  # noqa: F401 -- registers them
+    return torch.ops.sot_amd
+
+
+def _window_name(window) -> str:
+    return "" if window is None else str(window)
+
 
 def end_padded(signal: torch.Tensor, frame_size: int, hop: int) -> torch.Tensor:
     """Pad so that the window slides until it is completely beyond the signal (tf.stft(pad_end=True) semantics)."""
@@ -142,6 +154,9 @@ def stft_magnitude(audio: torch.Tensor, n_fft: int = 2048, hop: int = 256, windo
     (features.py:85-113).  GPU tensors run the HIP kernels (differentiable w.r.t. the audio); CPU tensors and sizes
     outside hip_stft_supported() run torch.stft."""
     if audio.is_cuda and audio.ndim == 2 and hip_stft_supported(n_fft, hop, audio.shape[1]):
+        if _compiling():
+            want_spec = SAVE_SPECTRUM and torch.is_grad_enabled() and audio.requires_grad
+            return _traced_ops().stft_magnitude(audio.float(), _window_name(window), int(n_fft), int(hop), want_spec)[0]
         if audio.dtype == torch.float32 and SAVE_SPECTRUM:
             from . import _native as nat
             glue = nat.glue()
@@ -196,6 +211,8 @@ def oscillator_bank(frequency_envelopes: torch.Tensor, amplitude_envelopes: torc
     muted.  GPU tensors run the HIP kernels (differentiable w.r.t. both envelopes), CPU tensors torch ops."""
     f, a = frequency_envelopes.float(), amplitude_envelopes.float()
     if f.is_cuda and f.ndim == 3 and f.shape == a.shape and 1 <= f.shape[1] <= (1 << 20) and 1 <= f.shape[2] <= 512:
+        if _compiling():
+            return _traced_ops().oscillator_bank(f, a, float(sample_rate))
         return _OscillatorBank.apply(f, a, float(sample_rate))
     a = torch.where(f >= sample_rate / 2.0, torch.zeros_like(a), a)
     phases = torch.cumsum(f * (2.0 * torch.pi) / float(sample_rate), dim=1)
@@ -322,7 +339,7 @@ def sinusoidal_synth(amplitudes: torch.Tensor, frequencies: torch.Tensor, n_samp
     MSS-LogLin runs): `frequency_filter` with the 128 taps of `roll_off_taps`, one filter shared by every clip, on every route."""
     signal = _sinusoidal_signal(amplitudes, frequencies, n_samples, sample_rate, harmonic)
     if apply_roll_off:
-        taps = roll_off_taps(signal.device)
+        taps = _traced_ops().roll_off_taps(signal.detach()) if (_compiling() and signal.is_cuda) else roll_off_taps(signal.device)
         signal = fft_convolve(signal, taps[None, :].expand(signal.shape[0], -1))
     return signal
 
@@ -330,6 +347,8 @@ def sinusoidal_synth(amplitudes: torch.Tensor, frequencies: torch.Tensor, n_samp
 def _sinusoidal_signal(amplitudes, frequencies, n_samples, sample_rate, harmonic):
     amplitudes, frequencies = amplitudes.float(), frequencies.float()
     if amplitudes.is_cuda and _envelope_kernels_apply(amplitudes, frequencies, n_samples, harmonic):
+        if _compiling():
+            return _traced_ops().synth(frequencies, amplitudes, int(n_samples), float(sample_rate), bool(harmonic))
         if FUSED_SYNTH:
             return _Synth.apply(frequencies, amplitudes, int(n_samples), float(sample_rate), bool(harmonic))
         freq_env, amp_env = _SynthEnvelopes.apply(frequencies, amplitudes, int(n_samples), float(sample_rate), bool(harmonic))
@@ -480,6 +499,8 @@ def fft_convolve(audio: torch.Tensor, impulse_response: torch.Tensor, padding: s
                   and nat.fir_in_domain(int(audio.shape[1]), taps, start))
         if on_hip:
             shared = impulse_response.shape[0] > 1 and impulse_response.stride(0) == 0
+            if _compiling():
+                return _traced_ops().fir_same(audio, impulse_response[0] if shared else impulse_response, start)
             return _FirSame.apply(audio, impulse_response[0] if shared else impulse_response, start)
         from .losses import warn_once
         warn_once(("fft_convolve", padding, bool(cross_fade), impulse_response.ndim, str(audio.dtype), str(impulse_response.dtype), taps, start),
@@ -609,6 +630,8 @@ def training_step_slice(loss_module, audio_target: torch.Tensor, audio_estimate:
     frequency positions, SOT loss (forward).  The caller backpropagates into `audio_estimate`.
     On the GPU, for the module's plain mean (no hinge) the slice is one autograd node (_AudioToLoss); otherwise it is the
     composition of stft_magnitude and the module."""
+    if _compiling() and audio_target.is_cuda:
+        return _traced_step_slice(loss_module, audio_target, audio_estimate, n_fft, hop, sample_rate, window)
     dev = audio_target.device
     key = (int(n_fft), float(sample_rate), str(dev))
     pos = _POSITIONS.get(key)
@@ -639,6 +662,25 @@ def training_step_slice(loss_module, audio_target: torch.Tensor, audio_estimate:
     spec_x = stft_magnitude(audio_target, n_fft, hop, window)
     spec_y = stft_magnitude(audio_estimate, n_fft, hop, window)
     return loss_module(spec_x, spec_y, x_pos=pos[0], y_pos=pos[1])
+
+
+def _traced_step_slice(loss_module, audio_target, audio_estimate, n_fft, hop, sample_rate, window):
+    """training_step_slice while torch.compile traces it: the same decision, the one-node form as the op sot_amd::audio_to_loss (which keeps
+    the position table and its plan inside), the composition on a copy of the table (sot_amd::unit_frequencies)."""
+    o = _traced_ops()
+    target_needs_grad = torch.is_grad_enabled() and audio_target.requires_grad
+    fused = (audio_target.ndim == 2 and audio_estimate.shape == audio_target.shape and hip_stft_supported(n_fft, hop, audio_target.shape[1])
+             and not getattr(loss_module, "hinge", False) and not target_needs_grad)
+    if fused:
+        from .losses import _flags
+        flags = _flags(loss_module.square_dist, bool(loss_module.dont_normalize), bool(loss_module.limit_quantile_range), loss_module.require_sort)
+        want_grad = torch.is_grad_enabled() and audio_estimate.requires_grad
+        return o.audio_to_loss(audio_target.float(), audio_estimate.float(), _window_name(window), int(n_fft), int(hop), float(sample_rate),
+                               float(loss_module.p), flags, want_grad)[0]
+    pos = o.unit_frequencies(audio_target.detach(), int(n_fft), float(sample_rate))
+    spec_x = stft_magnitude(audio_target, n_fft, hop, window)
+    spec_y = stft_magnitude(audio_estimate, n_fft, hop, window)
+    return loss_module(spec_x, spec_y, x_pos=pos, y_pos=pos.clone())
 
 
 def hz_to_unit(hz, hz_min=20.0, hz_max=8000.0, clip: bool = False) -> torch.Tensor:
@@ -690,15 +732,20 @@ def _fused_mix_step(loss_fn, x, x_hat, x_pos, y_pos, n_fft, hop, window, unit_po
     if not (L.EARLY_GRADIENT and SAVE_SPECTRUM and not sot.hinge and sot.require_sort and sot.p >= 1 and hip_stft_supported(n_fft, hop, samples)
             and 2 * bins <= 12000 and L._fresh_grid_ok(x_pos, x, bins) and L._fresh_grid_ok(y_pos, x, bins)):
         return None
-    glue = nat.glue()
-    if glue is None or not hasattr(glue, "mix_loss_step"):
+    glue = None if _compiling() else nat.glue()
+    if not _compiling() and (glue is None or not hasattr(glue, "mix_loss_step")):
         return None
     flags = L._flags(sot.square_dist, sot.dont_normalize, sot.limit_quantile_range, sot.require_sort)
     if getattr(sot, "tie_free_gradient", False):
         flags |= nat.FLAG_TIE_FREE_GRADIENT
-    total, mss_term, sot_term = glue.mix_loss_step(x, x_hat, _cached_window(window, n_fft, x.device), x_pos, y_pos, int(n_fft), int(hop), float(sot.p),
-                                                   int(flags), _cached_windows(None, sizes, x.device), list(sizes), float(mss.mag_weight),
-                                                   float(mss.logmag_weight), kind == "L2", w_mss, w_sot, bool(unit_positions))
+    if _compiling():   # the same kernel sequence as the C++ node, as one op
+        total, mss_term, sot_term, _ = _traced_ops().mix_loss_step(
+            x, x_hat, _window_name(window), x_pos, y_pos, int(n_fft), int(hop), float(sot.p), int(flags), list(sizes), float(mss.mag_weight),
+            float(mss.logmag_weight), kind == "L2", w_mss, w_sot, bool(unit_positions), grad_on and x_hat.requires_grad)
+    else:
+        total, mss_term, sot_term = glue.mix_loss_step(x, x_hat, _cached_window(window, n_fft, x.device), x_pos, y_pos, int(n_fft), int(hop), float(sot.p),
+                                                       int(flags), _cached_windows(None, sizes, x.device), list(sizes), float(mss.mag_weight),
+                                                       float(mss.logmag_weight), kind == "L2", w_mss, w_sot, bool(unit_positions))
     if terms is not None:   # what the trainer logs per loss (trainer.py:231-236): `(loss_fn(...) * weight).mean()`, values only
         for fn in fns:      # in the order of the mix, like the reference's dict
             terms[fn.__class__.__name__] = mss_term if fn is mss else sot_term
@@ -719,6 +766,8 @@ def trainer_loss_step(loss_fn, x: torch.Tensor, x_hat: torch.Tensor, n_fft: int 
     `terms`: a dict that receives the value of every loss of a mix by class name -- what the trainer logs as `loss/<step>/<name>`
     (trainer.py:231-236) -- detached; costs nothing in the one-node form (the node has both scalars anyway).
     A single loss that carries `log_scaled_x` gets `hz_to_unit` positions between `freq_hz_min` / `freq_hz_max` (trainer.py:187-191)."""
+    if positions is None and _compiling() and x.is_cuda:
+        positions = _traced_ops().bin_frequencies(x.detach(), int(n_fft), float(sample_rate))   # a copy of the table below, as a value of the traced graph
     if positions is None:
         # torch.tensor(self.transform.get_frequencies()).to(x.device) (trainer.py:192): the values depend on the transform alone, so the copy from the
         # host (pageable memory: a synchronising ~40 us per step, and impossible inside a stream capture) is made once per (n_fft, rate, device) and kept
