@@ -91,10 +91,12 @@ __device__ __forceinline__ float safe_logf(float x, float eps) { return logf(x <
 // range test of a frame's windowed samples (csrc/sot_stft.hip: frame_is_plain): then re^2 + im^2 of its bins neither overflows nor loses the bins that matter
 __device__ __forceinline__ bool frame_is_plain(float amax) { return (amax > 1e-9f && amax < 1e15f) || amax == 0.0f; }
 
-__device__ __forceinline__ float wave_max_f32(float v)
+// the maximum over the L consecutive lanes that hold one frame (L a power of two; L = 64: the wave)
+template <int L>
+__device__ __forceinline__ float frame_max_f32(float v)
 {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    for (int off = L / 2; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
     return v;
 }
 
@@ -187,8 +189,12 @@ __device__ __forceinline__ void window_frames(v2f (&rt)[16], v2f (&rv)[16], cons
         at = fmaxf(at, fmaxf(fabsf(rt[q].x), fabsf(rt[q].y)));
         av = fmaxf(av, fmaxf(fabsf(rv[q].x), fabsf(rv[q].y)));
     }
-    plain_t = __builtin_amdgcn_readfirstlane((int)frame_is_plain(wave_max_f32(at))) != 0;
-    plain_v = __builtin_amdgcn_readfirstlane((int)frame_is_plain(wave_max_f32(av))) != 0;
+    // Every FRAME is tested by itself (its L lanes), and the wave is plain when all its F frames are.  One test on the wave's maximum let a
+    // quiet frame ride on a loud neighbour -- 1e-21 noise beside an impulse -- into the plain path, where re^2 + im^2 is denormal: v_sqrt
+    // returns 0 for it, v_rsq infinity, and the gradient of the clip came out NaN (tests/test_signal_loops_gpu.py).  n_fft 2048 has one frame
+    // per wave (L = 64): the same test as before; no wave whose frames are all in range or all zero changes its path.
+    plain_t = __builtin_amdgcn_readfirstlane(__all((int)frame_is_plain(frame_max_f32<G::L>(at)))) != 0;
+    plain_v = __builtin_amdgcn_readfirstlane(__all((int)frame_is_plain(frame_max_f32<G::L>(av)))) != 0;
 }
 
 // The bin pairs of the lane: q < 8: k = L q + l (all lanes), q = 8: k = m / 2 (lane l = 0 of each frame).  With the packed transform Z,

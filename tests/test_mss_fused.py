@@ -116,6 +116,26 @@ def test_distance_kinds(kw):
     _check(MSSLoss(**kw), x, y, loss_tol=2e-5 if kw.get("logmag_weight") else 1e-5)
 
 
+@pytest.mark.parametrize("sizes", [(64,), (512,), (2048,), SIZES], ids=["64", "512", "2048", "all"])
+def test_quiet_frames_beside_a_loud_one(sizes):
+    """A wave of the fused kernel holds 2048 / n_fft frames.  1e-21 noise with one impulse: the frames the impulse is in are in the plain range of
+    |.|, their neighbours in the same wave are far below it (re^2 + im^2 denormal).  The range test is per frame: with one test on the wave's
+    maximum these clips had NaN gradients (v_rsq of a denormal is infinity).  Finite, and as close to float64 as the reference's float32."""
+    from gpu_util import device, native
+    from sot_amd.losses import MSSLoss
+    native()
+    g = torch.Generator().manual_seed(41)
+    samples = 3000
+    x = 1e-21 * (torch.rand(3, samples, generator=g) - 0.5)
+    y = 1e-21 * (torch.rand(3, samples, generator=g) - 0.5)
+    x[0, 700], y[0, 701], y[1, 2999], x[2, 5], y[2, 5] = 1.0, 0.3, 0.3, 1.0, 0.5
+    mod = MSSLoss(fft_sizes=sizes, mag_weight=1.0, logmag_weight=0.5)
+    yd = y.to(device()).requires_grad_(True)
+    mod(x.to(device()), yd).backward()
+    assert bool(torch.isfinite(yd.grad).all()), int((~torch.isfinite(yd.grad)).sum())
+    _check(mod, x, y, loss_tol=2e-5)
+
+
 def test_per_clip_means_with_weights():
     from gpu_util import native
     from sot_amd.losses import MSSLoss

@@ -131,3 +131,31 @@ def test_tie_free_shares_leave_half_of_the_sample_without_a_tie(n, m, B):
             srt = torch.sort(pos, 1)[0]
             tied |= (srt[:, 1:] == srt[:, :-1]).any(1)
         assert float((~tied).double().mean()) >= 0.52, (name, int((~tied).sum()), len(s))
+
+
+def test_clip_kinds_follow_each_other_at_every_grid_stride():
+    """tests/test_signal_loops_gpu.py: a workgroup's next clip is `stride` clips on; every ordered pair of kinds occurs at the strides the
+    capped grids have on 256 and 304 CUs (clips, workgroups of 16 / 8 / 4 frames of 9- and 17-frame clips) and at the small ones."""
+    for B, strides in ((513, (1, 2, 3, 7, 64, 256)), (609, (304,)), (2000, (128, 455, 512, 608))):      # 513 = 2 * 256 + 1 clips: the clip kernel's batch
+        kind = rk.clip_kind_ids(B)
+        assert torch.bincount(kind, minlength=len(rk.CLIP_KINDS)).min() >= B // 10
+        for stride in strides:
+            pairs = set(zip(kind[:-stride].tolist(), kind[stride:].tolist()))
+            assert len(pairs) == len(rk.CLIP_KINDS) ** 2, (B, stride, len(pairs))
+    other = rk.clip_kind_ids(B, salt=0x7E57)
+    assert 0.05 < float((other == kind).float().mean()) < 0.5      # an independent assignment: a target and an estimate of unlike kinds
+
+
+def test_clips_are_what_their_kind_says():
+    n_fft, hop, samples = 64, 16, 100
+    a, kind = rk.make_clips(400, samples, 1, n_fft, hop)
+    assert a.dtype == torch.float32 and a.shape == (400, samples) and bool(torch.isfinite(a).all())
+    of = lambda name: a[kind == rk.CLIP_KINDS.index(name)]      # noqa: E731
+    assert float(of("zeros").abs().max()) == 0.0
+    assert 0 < float(of("tiny").abs().max()) < 1e-21 and 1e5 < float(of("huge").abs().max()) <= 5e5
+    imp = of("impulse")
+    assert bool(((imp != 0).sum(1) == 1).all()) and bool((imp[:, :samples - hop] == 0).all()) and float(imp.max()) == 1.0
+    spec = torch.fft.rfft(of("tone")[:, :n_fft].double() * torch.hann_window(n_fft, dtype=torch.float64)).abs()
+    top = torch.topk(spec, 2, dim=1)
+    assert bool(((top.indices[:, 0] - top.indices[:, 1]).abs() == 1).all())      # between two bins: the two largest are neighbours ...
+    assert bool((top.values[:, 1] > 0.5 * top.values[:, 0]).all())               # ... of comparable size
