@@ -31,7 +31,7 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 18                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 19                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
 FIR_TILE = 1024                  # include/sot_hip.h: SOT_FIR_TILE (outputs per workgroup of the FIR kernel)
 FIR_MIN_TAPS, FIR_MAX_TAPS, FIR_MAX_SAMPLES = 3, 512, 1 << 20   # the FIR kernels' domain (include/sot_hip.h: sot_fir_same_forward)
@@ -81,6 +81,7 @@ EXPORTS = {
                                                    ctypes.c_size_t, _vp]),
     "sot_w1d_loss": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_double, ctypes.c_int, ctypes.c_float, _vp, _vp,
                                     _vp, _vp, ctypes.c_size_t, _vp]),
+    "sot_w1d_bf16_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SotProblem)]),
     "sot_w1d_quantiles": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp,
                                          ctypes.c_size_t, _vp]),
     "sot_w1d_quantiles_backward": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -141,6 +142,17 @@ EXPORTS = {
                                              ctypes.c_int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
+# The bfloat16 calls that enqueue work (ABI 19; `extern` in include/sot_hip.h).  A table of their own: tests/test_workspace_sizes.py holds
+# EXPORTS to the memory-contract table of tests/test_memory_contract_gpu.py entry by entry; these four have their guard-band cases in
+# tests/test_bf16_gpu.py.  load() binds both tables.
+BF16_EXPORTS = {
+    "sot_rows_bf16_to_f32": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int64, _vp]),
+    "sot_rows_f32_to_bf16": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int64, _vp]),
+    "sot_w1d_forward_bf16": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, ctypes.c_size_t, _vp]),
+    "sot_w1d_loss_bf16": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_double, ctypes.c_int, ctypes.c_float, _vp, _vp,
+                                         _vp, _vp, ctypes.c_size_t, _vp]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -167,7 +179,7 @@ def load(build_if_missing: bool = True):
         elif not os.path.exists(path):
             raise RuntimeError(f"{path} is missing")
         lib = ctypes.CDLL(path)
-        for name, (res, args) in EXPORTS.items():
+        for name, (res, args) in (*EXPORTS.items(), *BF16_EXPORTS.items()):
             fn = getattr(lib, name)  # AttributeError here = ABI mismatch, reported loudly
             fn.restype = res
             fn.argtypes = args
@@ -471,6 +483,78 @@ def loss_fused(x, y, xpos, ypos, p, flags, plan=None, denom=None, hinge=None, wa
                               _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
     check(rc, p)
     return mean, row_loss, total
+
+
+# ---- bfloat16 weight rows (include/sot_hip.h, ABI 19): row conversion and the typed forward.  Results are those of the float32 calls on
+# x.float(), y.float(), bit for bit; the row losses and the mean are float32.
+
+def _convert_rows(rows: torch.Tensor, src_dtype, dst_dtype, fn_name) -> torch.Tensor:
+    if not rows.is_cuda or rows.dtype != src_dtype or rows.ndim != 2:
+        raise TypeError(f"{fn_name} expects a 2-D {src_dtype} GPU tensor, got {rows.dtype} {tuple(rows.shape)} on {rows.device}")
+    rows = rows_view(rows)
+    B, n = rows.shape
+    out = torch.empty((B, n), dtype=dst_dtype, device=rows.device)
+    if B == 0 or n == 0:
+        return out
+    with _on_device(rows.device):
+        check(getattr(load(), fn_name)(rows.data_ptr(), B, n, rows.stride(0) if B > 1 else n, out.data_ptr(), n, stream_ptr(rows.device)))
+    return out
+
+
+def rows_to_f32(rows: torch.Tensor) -> torch.Tensor:
+    """[B, n] bfloat16 rows (unit inner stride, any row stride) -> dense float32 (sot_rows_bf16_to_f32; exact)."""
+    return _convert_rows(rows, torch.bfloat16, torch.float32, "sot_rows_bf16_to_f32")
+
+
+def rows_to_bf16(rows: torch.Tensor) -> torch.Tensor:
+    """[B, n] float32 rows -> dense bfloat16, round to nearest even (sot_rows_f32_to_bf16: the bits of torch's .to(torch.bfloat16))."""
+    return _convert_rows(rows, torch.float32, torch.bfloat16, "sot_rows_f32_to_bf16")
+
+
+def _require_bf16_rows(x, y, xpos, ypos):
+    require_hip(xpos, ypos)
+    for t in (x, y):
+        if not t.is_cuda or t.dtype != torch.bfloat16:
+            raise TypeError(f"the typed forward takes bfloat16 GPU weights for both measures; got {t.dtype} on {t.device}")
+
+
+def bf16_workspace(pr: SotProblem, device):
+    """The workspace of a typed call: exactly sot_w1d_bf16_workspace_bytes() -- the float32 call's own for a native problem, plus the two
+    widened copies for every other one -- or None when the call needs none."""
+    nbytes = int(load().sot_w1d_bf16_workspace_bytes(ctypes.byref(pr)))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes > 0 else None
+
+
+def forward_rows_bf16(x, y, xpos, ypos, p, flags, plan=None) -> torch.Tensor:
+    """row_loss[B] (float32) for bfloat16 weights x, y and float32 positions (sot_w1d_forward_bf16)."""
+    lib = load()
+    _require_bf16_rows(x, y, xpos, ypos)
+    dev = x.device
+    row_loss = torch.empty(x.shape[0], dtype=torch.float32, device=dev)
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = bf16_workspace(pr, dev)
+    with _on_device(dev):
+        rc = lib.sot_w1d_forward_bf16(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return row_loss
+
+
+def loss_fused_bf16(x, y, xpos, ypos, p, flags, plan=None, denom=None, hinge=None):
+    """Forward + batch mean for bfloat16 weights behind one call (sot_w1d_loss_bf16): (mean 0-d float32, row_loss [B] float32)."""
+    lib = load()
+    _require_bf16_rows(x, y, xpos, ypos)
+    dev = x.device
+    B = x.shape[0]
+    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = bf16_workspace(pr, dev)
+    with _on_device(dev):
+        rc = lib.sot_w1d_loss_bf16(ctypes.byref(pr), row_loss.data_ptr(), float(B if denom is None else denom), 0 if hinge is None else 1,
+                                   0.0 if hinge is None else float(hinge), mean.data_ptr(), None, None, _ptr(ws),
+                                   ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return mean, row_loss
 
 
 def prepared_loss_call(x, y, xpos, ypos, p, flags, plan, row_out, mean_out, sum_out=None, stream=None):

@@ -1,0 +1,247 @@
+// sot_bf16.hip -- bfloat16 weight rows (ABI 19): the two row-conversion kernels (bf16 -> f32, f32 -> bf16 with round to nearest even), the
+// instantiations of the full-row forward kernels that read 16-bit rows directly (sot_full_fwd.hpp: sot_area_full_kernel and
+// sot_forward_full_kernel with WT = uint16_t) and the typed entry points sot_w1d_forward_bf16 / sot_w1d_loss_bf16 with their workspace arithmetic.
+// A bfloat16 is the upper half of a float32, so widening is exact and "upcast, then the float32 arithmetic" defines every result: the
+// native kernels widen in the register behind the load, every other problem is widened into the workspace and takes run_forward as it is.
+#include "sot_full_fwd.hpp"
+
+namespace sot {
+
+// ---------------------------------------------------------------------------------------------
+// Row conversion.  A workgroup of 256 threads walks groups of `rpg` rows (as many short rows as its threads cover in one pass); a thread
+// owns chunks of CH consecutive elements: CH = 8 -- one 16-byte access on the 16-bit side, two on the 32-bit side -- where both pointers,
+// both strides and the length allow, CH = 1 (element-wise: rows that start 2 bytes off a boundary, odd lengths) otherwise.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)0x7FC0;      // NaN stays NaN (the payload is not kept)
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);       // ties to even; past the largest finite value: the carry makes +-inf
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void sot_rows_bf16_to_f32_kernel(const uint16_t* __restrict__ src, int64_t B, int n, int64_t ss,
+                                                                   float* __restrict__ dst, int64_t ds, int cpr, int rpg)
+{
+    const int64_t groups = (B + rpg - 1) / rpg;
+    const int units = rpg * cpr;   // <= 256 when rpg > 1; cpr when one row takes several passes
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        for (int i = threadIdx.x; i < units; i += 256) {
+            const int lr = i / cpr, c = i - lr * cpr;
+            const int64_t row = g * rpg + lr;
+            if (row >= B) continue;
+            const uint16_t* const s = src + row * ss + (int64_t)c * CH;
+            float* const d = dst + row * ds + (int64_t)c * CH;
+            if constexpr (CH == 8) {   // (c < n / 8: whole chunks inside the row)
+                const uint4 v = *reinterpret_cast<const uint4*>(s);
+                reinterpret_cast<float4*>(d)[0] = make_float4(__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u),
+                                                              __uint_as_float(v.y << 16), __uint_as_float(v.y & 0xFFFF0000u));
+                reinterpret_cast<float4*>(d)[1] = make_float4(__uint_as_float(v.z << 16), __uint_as_float(v.z & 0xFFFF0000u),
+                                                              __uint_as_float(v.w << 16), __uint_as_float(v.w & 0xFFFF0000u));
+            } else {
+                d[0] = __uint_as_float((uint32_t)s[0] << 16);
+            }
+        }
+    }
+}
+
+template <int CH>
+__global__ __launch_bounds__(256) void sot_rows_f32_to_bf16_kernel(const float* __restrict__ src, int64_t B, int n, int64_t ss,
+                                                                   uint16_t* __restrict__ dst, int64_t ds, int cpr, int rpg)
+{
+    const int64_t groups = (B + rpg - 1) / rpg;
+    const int units = rpg * cpr;
+    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
+        for (int i = threadIdx.x; i < units; i += 256) {
+            const int lr = i / cpr, c = i - lr * cpr;
+            const int64_t row = g * rpg + lr;
+            if (row >= B) continue;
+            const float* const s = src + row * ss + (int64_t)c * CH;
+            uint16_t* const d = dst + row * ds + (int64_t)c * CH;
+            if constexpr (CH == 8) {
+                const float4 a = reinterpret_cast<const float4*>(s)[0], b = reinterpret_cast<const float4*>(s)[1];
+                uint4 v;
+                v.x = (uint32_t)f32_to_bf16_rne(a.x) | ((uint32_t)f32_to_bf16_rne(a.y) << 16);
+                v.y = (uint32_t)f32_to_bf16_rne(a.z) | ((uint32_t)f32_to_bf16_rne(a.w) << 16);
+                v.z = (uint32_t)f32_to_bf16_rne(b.x) | ((uint32_t)f32_to_bf16_rne(b.y) << 16);
+                v.w = (uint32_t)f32_to_bf16_rne(b.z) | ((uint32_t)f32_to_bf16_rne(b.w) << 16);
+                *reinterpret_cast<uint4*>(d) = v;
+            } else {
+                d[0] = f32_to_bf16_rne(s[0]);
+            }
+        }
+    }
+}
+
+// chunks per row and rows per group of the conversion kernels, and their grid (eight 256-thread workgroups fill a CU's wave slots)
+struct ConvGeo { int cpr, rpg, grid; };
+static inline ConvGeo conv_geo(int64_t B, int n, int ch)
+{
+    ConvGeo g;
+    g.cpr = (n + ch - 1) / ch;
+    g.rpg = g.cpr >= 256 ? 1 : 256 / g.cpr;
+    g.grid = capped_grid((B + g.rpg - 1) / g.rpg, 8);
+    return g;
+}
+
+static int check_rows(const void* src, int64_t B, int32_t n, int64_t ss, const void* dst, int64_t ds)
+{
+    if (B < 0 || n < 1 || ss < n || ds < n) return SOT_ERR_BAD_SHAPE;
+    if (B > 0 && (src == nullptr || dst == nullptr)) return SOT_ERR_NULL_POINTER;
+    return SOT_OK;
+}
+
+int launch_rows_bf16_to_f32(const uint16_t* src, int64_t B, int n, int64_t ss, float* dst, int64_t ds, hipStream_t s)
+{
+    if (B == 0) return SOT_OK;
+    const bool vec = (n & 7) == 0 && (ss & 7) == 0 && (ds & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    const ConvGeo g = conv_geo(B, n, vec ? 8 : 1);
+    (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
+    if (vec) hipLaunchKernelGGL(sot_rows_bf16_to_f32_kernel<8>, dim3(g.grid), dim3(256), 0, s, src, B, n, ss, dst, ds, g.cpr, g.rpg);
+    else hipLaunchKernelGGL(sot_rows_bf16_to_f32_kernel<1>, dim3(g.grid), dim3(256), 0, s, src, B, n, ss, dst, ds, g.cpr, g.rpg);
+    return launch_status();
+}
+
+int launch_rows_f32_to_bf16(const float* src, int64_t B, int n, int64_t ss, uint16_t* dst, int64_t ds, hipStream_t s)
+{
+    if (B == 0) return SOT_OK;
+    const bool vec = (n & 7) == 0 && (ss & 3) == 0 && (ds & 7) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+    const ConvGeo g = conv_geo(B, n, vec ? 8 : 1);
+    (void)hipGetLastError();  // do not inherit a stale error from earlier runtime calls
+    if (vec) hipLaunchKernelGGL(sot_rows_f32_to_bf16_kernel<8>, dim3(g.grid), dim3(256), 0, s, src, B, n, ss, dst, ds, g.cpr, g.rpg);
+    else hipLaunchKernelGGL(sot_rows_f32_to_bf16_kernel<1>, dim3(g.grid), dim3(256), 0, s, src, B, n, ss, dst, ds, g.cpr, g.rpg);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Native 16-bit rows: the geometries that a row fills, on shared positions (the NX == 0 set without 8192 bins)
+// ---------------------------------------------------------------------------------------------
+static hipError_t dispatch_area_full_bf16(const FwdArgs& a, hipStream_t s)
+{
+    switch (a.n) {
+        case 512: return dispatch_area_full_bf16_g<64, 8, 4>(a, s);
+        case 1024: return dispatch_area_full_bf16_g<128, 8, 2>(a, s);
+        case 2048: return dispatch_area_full_bf16_g<256, 8, 1>(a, s);
+        case 4096: return dispatch_area_full_bf16_g<512, 8, 1>(a, s);
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
+static hipError_t dispatch_forward_full_bf16(int pm, const FwdArgs& a, hipStream_t s)
+{
+    switch (a.n) {
+        case 512: return dispatch_forward_full_bf16_g<64, 8, 4>(pm, a, s);
+        case 1024: return dispatch_forward_full_bf16_g<128, 8, 2>(pm, a, s);
+        case 2048: return dispatch_forward_full_bf16_g<256, 8, 1>(pm, a, s);
+        case 4096: return dispatch_forward_full_bf16_g<512, 8, 1>(pm, a, s);
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
+// The native route's condition (host side; sot_w1d_bf16_workspace_bytes reports by the same predicate): shared positions, n == m in the
+// set above, kernels with the length at compile time allowed, weights normalised by the call, rows of x and y on 16-byte boundaries
+// (pointer 16-byte aligned, row strides multiples of 8 elements).
+static inline bool bf16_native(const sot_problem* pr)
+{
+    return pr->xpos_row_stride == 0 && pr->ypos_row_stride == 0 && pr->n == pr->m &&
+           (pr->n == 512 || pr->n == 1024 || pr->n == 2048 || pr->n == 4096) &&
+           !(pr->flags & (SOT_FLAG_PRENORMALIZED | SOT_FLAG_NO_SPECIALIZE)) &&
+           ((reinterpret_cast<uintptr_t>(pr->x) | reinterpret_cast<uintptr_t>(pr->y)) & 15) == 0 && (pr->x_row_stride & 7) == 0 && (pr->y_row_stride & 7) == 0;
+}
+
+// widened copies at the front of the workspace: [x as float32, dense | y as float32, dense | the float32 call's own workspace]
+struct WidenLayout { size_t xf, yf, inner, total; };
+static inline WidenLayout widen_layout(const sot_problem* pr)
+{
+    WidenLayout w;
+    const size_t B = pr->B > 0 ? (size_t)pr->B : 0;
+    w.xf = 16;   // room to move the first copy up to a 16-byte boundary, whatever the workspace's own alignment
+    w.yf = w.xf + align_up(B * (size_t)pr->n * sizeof(float), 256);
+    w.inner = w.yf + align_up(B * (size_t)pr->m * sizeof(float), 256);
+    w.total = w.inner + sot_workspace_bytes(pr);
+    return w;
+}
+
+static int run_forward_bf16(const sot_problem* pr, float* row_loss, void* workspace, size_t workspace_bytes, void* stream, const MeanTail* mean_tail)
+{
+    int rc = validate(pr);
+    if (rc != SOT_OK) return rc;
+    if (bf16_native(pr)) {
+        Launch l;
+        rc = setup_launch(pr, false, workspace, workspace_bytes, stream, &l);   // positions, plan, flags: nothing in it follows x or y
+        if (rc != SOT_OK) return rc;
+        if (pr->B == 0) return SOT_OK;
+        l.a.row_loss = row_loss;
+        if (mean_tail != nullptr && row_loss != nullptr) l.a.mt = *mean_tail;
+        // the route family of run_forward for these rows: merge-free for p = 1 on one grid without cutoff, the merge walk otherwise
+        const bool area = l.pm == 1 && (pr->flags & SOT_FLAG_SAME_GRID) && !(pr->flags & (SOT_FLAG_LIMIT_Q | SOT_FLAG_NO_AREA));
+        return launch_status(area ? dispatch_area_full_bf16(l.a, l.s) : dispatch_forward_full_bf16(l.pm, l.a, l.s));
+    }
+    // every other problem: widen, then the float32 call as it is.  Refusals are decided before the conversions are enqueued.
+    {
+        LaunchCfg cfg; size_t lds; int block, rpw;
+        if (!pick_cfg(pr->n, pr->m, pr->xpos_row_stride != 0, false, &cfg, &lds, &block, &rpw)) return SOT_ERR_UNSUPPORTED_SIZE;
+    }
+    if (pr->B == 0) return run_forward(pr, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, stream, mean_tail);
+    const WidenLayout w = widen_layout(pr);
+    if (workspace == nullptr) return SOT_ERR_NULL_POINTER;
+    if (workspace_bytes < w.total) return SOT_ERR_WORKSPACE;
+    char* const base = reinterpret_cast<char*>(workspace);
+    const size_t lead = (size_t)((16 - (reinterpret_cast<uintptr_t>(base) & 15)) & 15);   // <= 15 < w.xf
+    float* const xf = reinterpret_cast<float*>(base + lead);
+    float* const yf = reinterpret_cast<float*>(base + lead + (w.yf - w.xf));
+    char* const inner = base + lead + (w.inner - w.xf);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    rc = launch_rows_bf16_to_f32(reinterpret_cast<const uint16_t*>(pr->x), pr->B, pr->n, pr->x_row_stride, xf, pr->n, s);
+    if (rc != SOT_OK) return rc;
+    rc = launch_rows_bf16_to_f32(reinterpret_cast<const uint16_t*>(pr->y), pr->B, pr->m, pr->y_row_stride, yf, pr->m, s);
+    if (rc != SOT_OK) return rc;
+    sot_problem wide = *pr;
+    wide.x = xf; wide.y = yf; wide.x_row_stride = pr->n; wide.y_row_stride = pr->m;
+    return run_forward(&wide, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, inner, w.total - w.inner, stream, mean_tail);
+}
+
+}  // namespace sot
+
+extern "C" {
+
+int sot_rows_bf16_to_f32(const uint16_t* src, int64_t B, int32_t n, int64_t src_row_stride, float* dst, int64_t dst_row_stride, void* stream)
+{
+    const int rc = sot::check_rows(src, B, n, src_row_stride, dst, dst_row_stride);
+    if (rc != SOT_OK) return rc;
+    return sot::launch_rows_bf16_to_f32(src, B, (int)n, src_row_stride, dst, dst_row_stride, reinterpret_cast<hipStream_t>(stream));
+}
+
+int sot_rows_f32_to_bf16(const float* src, int64_t B, int32_t n, int64_t src_row_stride, uint16_t* dst, int64_t dst_row_stride, void* stream)
+{
+    const int rc = sot::check_rows(src, B, n, src_row_stride, dst, dst_row_stride);
+    if (rc != SOT_OK) return rc;
+    return sot::launch_rows_f32_to_bf16(src, B, (int)n, src_row_stride, dst, dst_row_stride, reinterpret_cast<hipStream_t>(stream));
+}
+
+size_t sot_w1d_bf16_workspace_bytes(const sot_problem* prob)
+{
+    if (prob == nullptr || prob->n < 1 || prob->m < 1) return 0;
+    return sot::bf16_native(prob) ? sot_workspace_bytes(prob) : sot::widen_layout(prob).total;
+}
+
+int sot_w1d_forward_bf16(const sot_problem* prob, float* row_loss, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
+    return sot::run_forward_bf16(prob, row_loss, workspace, workspace_bytes, stream, nullptr);
+}
+
+int sot_w1d_loss_bf16(const sot_problem* prob, float* row_loss, double denom, int apply_hinge, float hinge_threshold, float* mean_out,
+                      double* sum_out, uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
+    if (mean_out == nullptr && sum_out == nullptr) return SOT_ERR_NULL_POINTER;
+    if (prob != nullptr && prob->B == 0) return SOT_ERR_BAD_SHAPE;  // the mean of zero rows is undefined
+    sot::MeanTail mt{};
+    mt.counters = completion_counters; mt.denom = denom; mt.apply_hinge = apply_hinge; mt.hinge = hinge_threshold; mt.mean_out = mean_out; mt.sum_out = sum_out;
+    const int rc = sot::run_forward_bf16(prob, row_loss, workspace, workspace_bytes, stream, completion_counters ? &mt : nullptr);
+    if (rc != SOT_OK || completion_counters != nullptr) return rc;
+    return sot_w1d_reduce_mean(row_loss, prob->B, denom, apply_hinge, hinge_threshold, mean_out, sum_out, stream);
+}
+
+}  // extern "C"

@@ -141,8 +141,19 @@ __device__ __forceinline__ void fetch_row_dwords_rt(const float* __restrict__ x,
 }
 
 // one row's loads in the form its geometry takes (NX == 0: 16-B loads, NX > 0: dword loads with a compile-time length, NX < 0: run time)
-template <int G, int CPT, int NX>
+// WT: the element type of the weight rows in memory -- float, or uint16_t for bfloat16 rows (NX == 0 only; a.x / a.y then point at 16-bit
+// elements and the row strides count them).  A fetched bfloat16 is widened in the register, float(bits << 16): exact, so everything behind
+// the fetch is the float32 code and returns the bits of the float32 call on the upcast rows.
+template <int G, int CPT, int NX, class WT = float>
 __device__ __forceinline__ void fetch_row(const float* __restrict__ x, const float* __restrict__ y, int t, int n, float (&rx)[CPT], float (&ry)[CPT]);
+
+// row r of a weight array whose elements are WT and whose row stride counts them (the pointer travels as const float* whatever WT is)
+template <class WT>
+__device__ __forceinline__ const float* weight_row(const float* base, int64_t r, int64_t stride)
+{
+    if constexpr (std::is_same<WT, float>::value) return base + r * stride;
+    else return reinterpret_cast<const float*>(reinterpret_cast<const WT*>(base) + r * stride);
+}
 
 template <int G, int CPT>
 __device__ __forceinline__ void fetch_full_row(const float* __restrict__ x, const float* __restrict__ y, int t, float (&rx)[CPT],
@@ -168,15 +179,27 @@ __device__ __forceinline__ void fetch_full_row(const float* __restrict__ x, cons
 // rx[k] = step k, ry[k] = step 8 + k of the thread's task (both of ONE array).
 // forward kernels in square_dist mode stage the SQUARED weights (the chunk sums need the squares anyway; the owner's division then reads
 // them instead of squaring again); the backward kernels keep the raw weights (their output arithmetic needs them)
-template <int G, int CPT>
+// WT = uint16_t (bfloat16 rows): the same tasks, the same registers and therefore the same summation order, read with 16-bit loads -- per
+// load instruction a wave then touches two half-used 128-byte lines, which the 16 steps of the task use up between them.
+template <int G, int CPT, class WT = float>
 __device__ __forceinline__ void fetch_row_columns(const float* __restrict__ x, const float* __restrict__ y, int t, float (&rx)[CPT], float (&ry)[CPT])
 {
     static_assert(CPT == 8, "16 steps per task: two registers arrays of 8");
     const bool isy = t >= G / 2;
     const int task = isy ? t - G / 2 : t;
-    const float* const src = (isy ? y : x) + ((task >> 5) << 9) + (task & 31);
+    if constexpr (std::is_same<WT, float>::value) {
+        const float* const src = (isy ? y : x) + ((task >> 5) << 9) + (task & 31);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { rx[k] = src[k << 5]; ry[k] = src[(8 + k) << 5]; }
+        for (int k = 0; k < 8; ++k) { rx[k] = src[k << 5]; ry[k] = src[(8 + k) << 5]; }
+    } else {
+        static_assert(std::is_same<WT, uint16_t>::value, "weight rows are float32 or bfloat16");
+        const uint16_t* const src = reinterpret_cast<const uint16_t*>(isy ? y : x) + ((task >> 5) << 9) + (task & 31);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            rx[k] = __uint_as_float((uint32_t)src[k << 5] << 16);
+            ry[k] = __uint_as_float((uint32_t)src[(8 + k) << 5] << 16);
+        }
+    }
 }
 
 // The same for the one-sided spectra (NX = 129 / 257 / 513 / 1025 / 2049 bins on their odd geometries): the 2 NT = 64 ceil(NSTEPS / 16) tasks
@@ -216,10 +239,11 @@ __device__ __forceinline__ void fetch_row_columns_nx(const float* __restrict__ x
     column_slot<CPT>(rx, ry, C::NV) = tail;
 }
 
-template <int G, int CPT, int NX>
+template <int G, int CPT, int NX, class WT>
 __device__ __forceinline__ void fetch_row(const float* __restrict__ x, const float* __restrict__ y, int t, int n, float (&rx)[CPT], float (&ry)[CPT])
 {
-    if constexpr (NX == 0) fetch_row_columns<G, CPT>(x, y, t, rx, ry);
+    static_assert(std::is_same<WT, float>::value || NX == 0, "16-bit rows: the geometries that a row fills (16-byte aligned rows) only");
+    if constexpr (NX == 0) fetch_row_columns<G, CPT, WT>(x, y, t, rx, ry);
     else if constexpr (NX > 0 && ColumnsNX<G, CPT, (NX > 0 ? NX : 129)>::OK) fetch_row_columns_nx<G, CPT, NX>(x, y, t, rx, ry);
     else if constexpr (NX == 0) fetch_full_row<G, CPT>(x, y, t, rx, ry);
     else if constexpr (NX > 0) fetch_row_dwords<G, CPT, NX>(x, y, t, rx, ry);
@@ -378,12 +402,13 @@ struct NoRowHook { __device__ __forceinline__ void operator()() const {} };   //
 // nothing is written to U / V and the closing barrier is left out (the barrier behind the raw reads already orders the next
 // row's staging behind this row's last LDS read of the raw weights).
 // RAW_OUT: wx / wy must be the weights as given (a gradient needs them); otherwise square_dist rows may be staged as their squares
+// WT: the weight rows' element type in memory (fetch_row), which only the next-row prefetch at the end sees.
 // PLAIN (the fast body of sot_area_full_kernel): the caller has checked, once per launch, that both permutations are the identity and
 // that the rows are normalised; c.dn / c.x_ident / c.y_ident are then compile-time constants here and the permuted owner reads are not
 // compiled.  after_b1(): called by every thread behind barrier 1 (that body's deferred row-loss store).  PLAIN and after_b1 belong to
 // that one caller: the merge, backward and training kernels leave both at their defaults.
 template <int G, int CPT, int ROWS, int GRAD, bool SQ, int NX = 0, bool TO_LDS = true, bool RAW_OUT = (GRAD != 0), bool PLAIN = false,
-          class AfterB1 = NoRowHook>
+          class AfterB1 = NoRowHook, class WT = float>
 __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx& c, float (&rx)[CPT], float (&ry)[CPT],
                                                 const float* nxt_x, const float* nxt_y, float (&wx)[CPT], float (&wy)[CPT],
                                                 float& Sx, float& Sy, float (&cu)[CPT], float (&cv)[CPT], unsigned long long* sacc = nullptr,
@@ -654,7 +679,7 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     // phases, whose register demand is small, instead of across the register-hungry division / scan (8192 x 2048: 45.6 -> 44.8 us).
     // The merge-free kernel has no walk to hide them behind, yet issuing them right behind barrier 1 in its plain loop (no more
     // registers: 118 either way) was slower, 33.4 against 32.2 us per headline step (profiles/f8_area_plain_loop.txt)
-    if (nxt_x != nullptr) fetch_row<G, CPT, NX>(nxt_x, nxt_y, t, a.n, rx, ry);
+    if (nxt_x != nullptr) fetch_row<G, CPT, NX, WT>(nxt_x, nxt_y, t, a.n, rx, ry);
     if constexpr (TO_LDS) row_sync<NW>();
 }
 

@@ -91,9 +91,12 @@ constexpr int kRt512MinWaves = 4;
 // forward): every row brings its own positions -- loaded coalesced, staged in the U / V regions, gathered through the permutation into the
 // position copy behind the row region -- and its weights are read through the same permutation (the psx / psy path of a permuted shared grid).
 // One row per workgroup only (the position copy is the row's own), rows that fill their geometry (NX == 0).
-template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX = 0, bool RP = false>
+// WT (sot_full_common.hpp: fetch_row): the element type of the weight rows in memory -- float, or uint16_t for bfloat16 rows (a.x / a.y then
+// point at 16-bit elements, a.xs / a.ys count them; NX == 0 on shared positions only).  Only the two fetches see it.
+template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX = 0, bool RP = false, class WT = float>
 __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? kRt512MinWaves : (CPT == 17) ? kFwd17MinWaves : kFwdMinWaves) void sot_forward_full_kernel(const FwdArgs a)
 {
+    static_assert(std::is_same<WT, float>::value || (NX == 0 && !RP), "16-bit rows: rows that fill their geometry, shared positions");
     static_assert(!RP || (ROWS == 1 && NX == 0 && CPT == 8), "per-row positions: one row per workgroup, rows that fill the 8-element geometry");
     using Geo = FullGeo<G, CPT, ROWS, false, NX>;
     constexpr FullLayout L = Geo::L;
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? kRt512MinWaves : (
     const float* const Uw = c.Uw;
     if (row0 < a.B) {
         const int64_t r = min(row0 + rg, a.B - 1);
-        fetch_row<G, CPT, NX>(a.x + r * a.xs, a.y + r * a.ys, t, a.n, rx, ry);
+        fetch_row<G, CPT, NX, WT>(weight_row<WT>(a.x, r, a.xs), weight_row<WT>(a.y, r, a.ys), t, a.n, rx, ry);
     }
 
 #ifdef SOT_STAMPS
@@ -141,9 +144,9 @@ __global__ __launch_bounds__(ROWS * G, (G == 512 && NX < 0) ? kRt512MinWaves : (
             int ix[CPT], iy[CPT];
             rowpos_row_setup<G, CPT, ROWS, false, NX>(a, c, min(row, a.B - 1), ix, iy, psx, psy);
         }
-        full_build_cdfs<G, CPT, ROWS, false, SQ, NX>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
-                                                     more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc, HOIST_PERM ? psx : nullptr,
-                                                     HOIST_PERM ? psy : nullptr);
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, true, false, false, NoRowHook, WT>(
+            a, c, rx, ry, more ? weight_row<WT>(a.x, rn, a.xs) : nullptr, more ? weight_row<WT>(a.y, rn, a.ys) : nullptr, wx, wy, Sx, Sy, cu, cv, sacc,
+            HOIST_PERM ? psx : nullptr, HOIST_PERM ? psy : nullptr);
         SOT_PH(sacc, 9);   // wave totals, CDF values to LDS, next row's loads issued, barrier
 
         // ---- P4: merge of the two CDFs (losses.py:295-313), E steps per thread
@@ -238,7 +241,7 @@ constexpr int kAreaMinWaves = 1;
 template <int G, int CPT, int ROWS, int NX>
 constexpr bool kAreaPlainLoop = (G == 256 && CPT == 8 && ROWS == 1 && NX == 0);
 
-template <int G, int CPT, int ROWS, bool SQ, int NX>
+template <int G, int CPT, int ROWS, bool SQ, int NX, class WT = float>
 __device__ __forceinline__ void area_rows_plain(const FwdArgs& a, const FullCtx& c, float (&rx)[CPT], float (&ry)[CPT], const float (&dx)[CPT],
                                                 int64_t row0, int64_t row_step, unsigned long long* sacc)
 {
@@ -268,9 +271,9 @@ __device__ __forceinline__ void area_rows_plain(const FwdArgs& a, const FullCtx&
 #ifdef SOT_STAMPS
         if (sacc != nullptr) sacc[15] = __builtin_readcyclecounter();
 #endif
-        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, false, true>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
-                                                                         more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc,
-                                                                         nullptr, nullptr, store_pending);
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, false, true, std::remove_const_t<decltype(store_pending)>, WT>(
+            a, c, rx, ry, more ? weight_row<WT>(a.x, rn, a.xs) : nullptr, more ? weight_row<WT>(a.y, rn, a.ys) : nullptr, wx, wy, Sx, Sy, cu, cv, sacc,
+            nullptr, nullptr, store_pending);
         SOT_PH(sacc, 9);   // wave totals, CDF values, next row's loads issued
         float acc = 0.0f;
 #pragma unroll
@@ -296,7 +299,7 @@ __device__ __forceinline__ void area_rows_plain(const FwdArgs& a, const FullCtx&
     }
 }
 
-template <int G, int CPT, int ROWS, bool SQ, int NX = 0>
+template <int G, int CPT, int ROWS, bool SQ, int NX = 0, class WT = float>
 __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWaves) void sot_area_full_kernel(const FwdArgs a)
 {
     using Geo = FullGeo<G, CPT, ROWS, false, NX>;
@@ -315,7 +318,7 @@ __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWa
     float rx[CPT], ry[CPT];
     if (row0 < a.B) {
         const int64_t r = min(row0 + rg, a.B - 1);
-        fetch_row<G, CPT, NX>(a.x + r * a.xs, a.y + r * a.ys, t, a.n, rx, ry);
+        fetch_row<G, CPT, NX, WT>(weight_row<WT>(a.x, r, a.xs), weight_row<WT>(a.y, r, a.ys), t, a.n, rx, ry);
     }
     c.dn = a.flags & SOT_FLAG_DONT_NORMALIZE;
     float* const base = smem + rg * L.rowf;
@@ -350,7 +353,7 @@ __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWa
     bool plain = false;
     if constexpr (PLAIN_LOOP) plain = c.x_ident && c.y_ident && !c.dn && a.row_loss != nullptr && a.mt.counters == nullptr;
     if (plain) {
-        if constexpr (PLAIN_LOOP) area_rows_plain<G, CPT, ROWS, SQ, NX>(a, c, rx, ry, dx, row0, row_step, sacc);
+        if constexpr (PLAIN_LOOP) area_rows_plain<G, CPT, ROWS, SQ, NX, WT>(a, c, rx, ry, dx, row0, row_step, sacc);
     } else {
     for (; row0 < a.B; row0 += row_step) {
         const int64_t row = row0 + rg;
@@ -361,12 +364,12 @@ __global__ __launch_bounds__(ROWS * G, (CPT == 17) ? kFwd17MinWaves : kAreaMinWa
         float Sx, Sy;
 #ifdef SOT_STAMPS
         if (sacc != nullptr) sacc[15] = __builtin_readcyclecounter();
-        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
-                                                            more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc);
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, false, false, NoRowHook, WT>(
+            a, c, rx, ry, more ? weight_row<WT>(a.x, rn, a.xs) : nullptr, more ? weight_row<WT>(a.y, rn, a.ys) : nullptr, wx, wy, Sx, Sy, cu, cv, sacc);
         SOT_PH(sacc, 9);   // wave totals, CDF values, next row's loads issued
 #else
-        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
-                                                            more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv);
+        full_build_cdfs<G, CPT, ROWS, false, SQ, NX, false, false, false, NoRowHook, WT>(
+            a, c, rx, ry, more ? weight_row<WT>(a.x, rn, a.xs) : nullptr, more ? weight_row<WT>(a.y, rn, a.ys) : nullptr, wx, wy, Sx, Sy, cu, cv);
 #endif
         float acc = 0.0f;
 #pragma unroll
@@ -636,6 +639,28 @@ static hipError_t launch_area_full(const FwdArgs& a, hipStream_t s)
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
     return launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, SQ, NX>>(a, sizeof(float) * (size_t)ROWS * (size_t)L.rowf, (a.B + ROWS - 1) / ROWS,
                                                                                ROWS * G, s);
+}
+
+// the bfloat16 instantiations (WT = uint16_t): same LDS layout, block and row groups as the float32 launch of the geometry
+template <int G, int CPT, int ROWS>
+static hipError_t dispatch_area_full_bf16_g(const FwdArgs& a, hipStream_t s)
+{
+    constexpr FullLayout L = full_layout<G, CPT, ROWS, false, 0>();
+    constexpr size_t lds = sizeof(float) * (size_t)ROWS * (size_t)L.rowf;
+    return (a.flags & SOT_FLAG_SQUARE) ? launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, true, 0, uint16_t>>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * G, s)
+                                       : launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, false, 0, uint16_t>>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * G, s);
+}
+
+template <int G, int CPT, int ROWS>
+static hipError_t dispatch_forward_full_bf16_g(int pm, const FwdArgs& a, hipStream_t s)
+{
+    constexpr FullLayout L = full_layout<G, CPT, ROWS, false, 0>();
+    static_assert(sizeof(float) * (size_t)L.total <= kLdsLimit, "workgroup fits one CU's LDS");
+    return with_mode(pm, a.flags, [&](auto md) {
+        using M = decltype(md);
+        return launch_persistent_profiled<sot_forward_full_kernel<G, CPT, ROWS, M::PM, M::LIM, M::SQ, 0, false, uint16_t>>(a, sizeof(float) * (size_t)L.total,
+                                                                                                          (a.B + ROWS - 1) / ROWS, ROWS * G, s);
+    });
 }
 
 template <int G, int CPT, int ROWS, int NX = 0>

@@ -8,7 +8,9 @@ Same names, argument meaning and error behaviour as the reference's ``losses`` m
 ``class_path: losses.Wasserstein1D`` keep working unchanged.
 
 All arithmetic on float32 HIP-device tensors runs in the hand-written HIP library (csrc/, C ABI in
-include/sot_hip.h); this file only reshapes, marshals pointers and wires autograd.  Tensors outside the library's domain
+include/sot_hip.h); this file only reshapes, marshals pointers and wires autograd.  bfloat16 weights on the device (autocast) are
+the float32 call on the exactly widened rows: the typed forward where no gradient is asked for, a widening kernel in front of the
+float32 path -- and a narrowing one behind its gradient -- where one is (_hip_domain).  Tensors outside the library's domain
 -- CPU tensors, float64 -- take the reference's own route, torch ops (_torch_path.py), because the reference is device- and
 dtype-agnostic (losses.py:129-211) and `accelerator: cpu` has to keep working.
 """
@@ -50,13 +52,18 @@ def warn_once(key, message):
         warnings.warn(message, stacklevel=3)
 
 
-def _hip_domain(*tensors) -> bool:
-    """True when the HIP library takes these tensors: all of them float32 on a HIP device.  CPU tensors (any floating dtype) and
-    float64 tensors (any device) go to the torch-op composition instead -- float64 is then float64 arithmetic, as in the
-    reference; a float64 GPU tensor says so once.  half / bfloat16 GPU tensors are refused (TypeError), not upcast."""
-    ts = [t for t in tensors if t is not None]
-    if all(t.is_cuda and t.dtype == torch.float32 for t in ts):
-        return True
+def _hip_domain(x, y, *positions) -> bool:
+    """True when the HIP library takes these tensors (the two weight tensors first, then the positions): all of them on a HIP device, the
+    positions float32 and the weights either both float32 or both bfloat16 -- what a model under torch.autocast(dtype=torch.bfloat16)
+    hands over; widening a bfloat16 is exact, so such a call is DEFINED as the float32 call on x.float(), y.float() and returns its bits
+    (the loss in float32, the gradient of a bfloat16 operand in bfloat16, rounded to nearest even).  CPU tensors (any floating dtype) and
+    float64 tensors (any device) go to the torch-op composition instead -- float64 is then float64 arithmetic, as in the reference; a
+    float64 GPU tensor says so once.  half GPU tensors (another exponent range), a float32 / bfloat16 mix and bfloat16 positions are
+    refused (TypeError), not upcast."""
+    ts = [t for t in (x, y) + positions if t is not None]
+    if all(t.is_cuda for t in ts) and all(t.dtype == torch.float32 for t in positions if t is not None):
+        if x.dtype == y.dtype and x.dtype in (torch.float32, torch.bfloat16):
+            return True
     for t in ts:
         if t.is_cuda and t.dtype in (torch.float16, torch.bfloat16):
             raise TypeError(f"sot_amd computes in float32; got {t.dtype} (convert with .float())")
@@ -64,6 +71,35 @@ def _hip_domain(*tensors) -> bool:
         warn_once("not-hip-f32", "sot_amd: tensors that are not all float32 on the GPU (float64, or CPU and GPU mixed) run the torch-op "
                                  "composition in their own dtype, like the reference; the HIP kernels take float32 GPU tensors")
     return False
+
+
+class _RowsToF32(torch.autograd.Function):
+    """[rows, n] bfloat16 -> float32 (sot_rows_bf16_to_f32); the gradient comes back narrowed to bfloat16 (sot_rows_f32_to_bf16)."""
+
+    @staticmethod
+    def forward(ctx, rows):
+        return nat.rows_to_f32(rows)
+
+    @staticmethod
+    def backward(ctx, g):
+        return nat.rows_to_bf16(g.float())
+
+
+def _widen(t):
+    """A bfloat16 weight tensor of any leading shape as float32, attached to autograd through the narrowing kernel."""
+    rows = t.reshape(-1, t.shape[-1])
+    out = _o.rows_to_f32(rows) if _compiling() else _RowsToF32.apply(rows)
+    return out.reshape(t.shape)
+
+
+def _typed_forward_applies(x, y, xpos, ypos, return_quantiles=False) -> bool:
+    """bfloat16 weights: does the call take the typed forward (sot_w1d_forward_bf16 / sot_w1d_loss_bf16 -- 16-bit row loads in the kernel on
+    the headline and paper shapes, widening inside the call elsewhere)?  Calls that need no gradient do: torch.no_grad, inference_mode,
+    operands without requires_grad.  Calls that need one, return_quantiles and the mixed-supports route widen x and y first (_widen) and
+    follow the float32 path unchanged."""
+    if return_quantiles or mixed_route_applies(x, y, xpos, ypos):
+        return False
+    return not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)))
 
 
 ROW_SIDE_LIMIT = 16384    # points of ONE side (csrc/sot_launch.hpp pick_cfg: at most 1024 threads x 16 points per row)
@@ -424,9 +460,13 @@ def wasserstein_1d(u_values, v_values, u_weights=None, v_weights=None, p=1, requ
         u_weights = torch.full(u_values.shape, 1.0 / n, device=u_values.device, dtype=u_values.dtype)
     if v_weights is None:
         v_weights = torch.full(v_values.shape, 1.0 / m, device=v_values.device, dtype=v_values.dtype)
-    if not _hip_domain(u_values, v_values, u_weights, v_weights) or _beyond_one_cu(u_weights, v_weights, u_values, v_values):
+    if not _hip_domain(u_weights, v_weights, u_values, v_values) or _beyond_one_cu(u_weights, v_weights, u_values, v_values):
+        if u_weights.is_cuda and u_weights.dtype is torch.bfloat16:   # (rows beyond one CU's LDS: the composition on the upcast weights)
+            u_weights, v_weights = u_weights.float(), v_weights.float()
         return tp.transport_rows(u_values, v_values, u_weights, v_weights, p=p, require_sort=require_sort,
                                  return_quantiles=return_quantiles, limit_quantile_range=limit_quantile_range)
+    if u_weights.dtype is torch.bfloat16 and not _typed_forward_applies(u_weights, v_weights, u_values, v_values, return_quantiles):
+        u_weights, v_weights = _widen(u_weights), _widen(v_weights)
 
     if mixed_route_applies(u_weights, v_weights, u_values, v_values, return_quantiles):
         flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
@@ -436,11 +476,13 @@ def wasserstein_1d(u_values, v_values, u_weights=None, v_weights=None, p=1, requ
     def shared_row(t):
         return t[0] if (t.ndim == 2 and t.shape[0] > 1 and t.stride(0) == 0) else t
     upos, vpos = shared_row(u_values), shared_row(v_values)
-    x, y, upos, vpos = _prepare(u_weights, v_weights, upos, vpos)
+    x, y, upos, vpos = _prepare(u_weights, v_weights, upos, vpos, checked=True)   # (_hip_domain above)
     flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
     plan = _functional_plans.get(upos, vpos) if (require_sort and upos.ndim == 1 and not _compiling()) else None
     if return_quantiles:
         return _quantile_tensors(x, y, upos, vpos, float(p), flags, plan)
+    if x.dtype is torch.bfloat16:   # no gradient asked for: the typed forward
+        return _o.w1d_rows_bf16(x, y, upos, vpos, float(p), flags) if _compiling() else nat.forward_rows_bf16(x, y, upos, vpos, float(p), flags, plan)
     if _compiling():
         return _o.w1d_rows(x, y, upos, vpos, float(p), flags)
     return _RowLoss.apply(x, y, upos, vpos, float(p), flags, plan)
@@ -586,6 +628,8 @@ class Wasserstein1D(torch.nn.Module):
 
     def _torch_forward(self, x, y, x_pos_, y_pos_, kwargs, rows_only=False):
         """CPU / float64 tensors: the torch-op composition (_torch_path.py), same keyword handling as the HIP route."""
+        if x.is_cuda and x.dtype is torch.bfloat16 and y.dtype is torch.bfloat16:   # (rows beyond one CU's LDS: on the upcast weights)
+            x, y = x.float(), y.float()
         return tp.module_forward(
             x, y, x_pos_, y_pos_, p=self.p, square_dist=self.square_dist,
             dont_normalize=bool(kwargs.get("dont_normalize", False) or self.dont_normalize),
@@ -600,11 +644,16 @@ class Wasserstein1D(torch.nn.Module):
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
         if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
             return self._torch_forward(x, y, x_pos_, y_pos_, kwargs, rows_only=True)
+        if x.dtype is torch.bfloat16 and not _typed_forward_applies(x, y, x_pos_, y_pos_):
+            x, y = _widen(x), _widen(y)
         if mixed_route_applies(x, y, x_pos_, y_pos_):   # a shared grid against per-row positions: nothing is materialised
             loss = _mixed_row_losses(x, y, x_pos_, y_pos_, self.p, self._flag_word(kwargs), self._plans)
         else:
             x, y, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
-            if _compiling():
+            if x.dtype is torch.bfloat16:   # no gradient asked for: the typed forward
+                loss = (_o.w1d_rows_bf16(x, y, x_pos_, y_pos_, float(self.p), flags) if _compiling()
+                        else nat.forward_rows_bf16(x, y, x_pos_, y_pos_, float(self.p), flags, plan))
+            elif _compiling():
                 loss = _o.w1d_rows(x, y, x_pos_, y_pos_, float(self.p), flags)
             elif torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, x_pos_, y_pos_)):
                 loss = _RowLoss.apply(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
@@ -653,6 +702,8 @@ class Wasserstein1D(torch.nn.Module):
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
         if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
             return self._torch_forward(x, y, x_pos_, y_pos_, kwargs)
+        if x.dtype is torch.bfloat16 and not _typed_forward_applies(x, y, x_pos_, y_pos_, kwargs.get("return_quantiles", False)):
+            x, y = _widen(x), _widen(y)   # a gradient is asked for (or quantiles, mixed supports): the float32 path, gradients narrowed
         return self._hip_forward(x, y, x_pos, y_pos, x_pos_, y_pos_, kwargs)
 
     def _hip_forward(self, x, y, x_pos, y_pos, x_pos_, y_pos_, kwargs):
@@ -667,6 +718,10 @@ class Wasserstein1D(torch.nn.Module):
             # default reduction: forward and the mean over every row (losses.py:211) in one native call
             x2, y2, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
             grad_on = torch.is_grad_enabled()
+            if x2.dtype is torch.bfloat16:   # no gradient asked for (forward): the typed forward + batch mean, one native call
+                if _compiling():
+                    return _o.w1d_mean_bf16(x2, y2, x_pos_, y_pos_, float(self.p), flags)
+                return nat.loss_fused_bf16(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)[0]
             if _compiling():   # the same two native calls as below, as ops: the training form when only y (and positions) ask for a gradient
                 if grad_on and EARLY_GRADIENT and y2.requires_grad and not x2.requires_grad:
                     return _o.w1d_mean_and_grad(x2, y2, x_pos_, y_pos_, float(self.p), flags)[0]

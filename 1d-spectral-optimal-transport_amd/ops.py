@@ -710,6 +710,115 @@ def _fir_backward(ctx, grad_out):
 
 fir_same.register_autograd(_fir_backward, setup_context=_fir_setup)
 
+# ---------------------------------------------------------------- bfloat16 weight rows (include/sot_hip.h, ABI 19)
+
+@custom_op("sot_amd::rows_to_f32", mutates_args=(), device_types="cuda")
+def rows_to_f32(rows: Tensor) -> Tensor:
+    """[B, n] bfloat16 rows -> dense float32 (sot_rows_bf16_to_f32; exact).  Backward: rows_to_bf16 of the incoming gradient."""
+    CALLS["rows_to_f32"] += 1
+    return nat.rows_to_f32(rows)
+
+
+@rows_to_f32.register_fake
+def _(rows):
+    return rows.new_empty(rows.shape, dtype=torch.float32)
+
+
+@custom_op("sot_amd::rows_to_bf16", mutates_args=(), device_types="cuda")
+def rows_to_bf16(rows: Tensor) -> Tensor:
+    """[B, n] float32 rows -> dense bfloat16, round to nearest even (sot_rows_f32_to_bf16).  Backward: rows_to_f32 of the gradient."""
+    CALLS["rows_to_bf16"] += 1
+    return nat.rows_to_bf16(rows.float())
+
+
+@rows_to_bf16.register_fake
+def _(rows):
+    return rows.new_empty(rows.shape, dtype=torch.bfloat16)
+
+
+def _no_setup(ctx, inputs, output):
+    pass
+
+
+def _rows_to_f32_backward(ctx, g):
+    return (torch.ops.sot_amd.rows_to_bf16(g),)
+
+
+def _rows_to_bf16_backward(ctx, g):
+    return (torch.ops.sot_amd.rows_to_f32(g),)
+
+
+rows_to_f32.register_autograd(_rows_to_f32_backward, setup_context=_no_setup)
+rows_to_bf16.register_autograd(_rows_to_bf16_backward, setup_context=_no_setup)
+
+
+@custom_op("sot_amd::w1d_rows_bf16", mutates_args=(), device_types="cuda")
+def w1d_rows_bf16(x: Tensor, y: Tensor, xpos: Tensor, ypos: Tensor, p: float, flags: int) -> Tensor:
+    """float32 rows[B] = W_p^p per pair of bfloat16 weight rows (sot_w1d_forward_bf16): shared or per-row float32 positions."""
+    CALLS["w1d_rows_bf16"] += 1
+    x, y, xpos, ypos, mixed, plan = _marshal(x, y, xpos, ypos, flags)
+    if mixed:
+        raise RuntimeError("sot_amd::w1d_rows_bf16 takes both position tensors of one kind (widen with rows_to_f32 for mixed supports)")
+    return nat.forward_rows_bf16(x, y, xpos, ypos, p, flags, plan)
+
+
+@w1d_rows_bf16.register_fake
+def _(x, y, xpos, ypos, p, flags):
+    return x.new_empty(x.shape[0], dtype=torch.float32)
+
+
+@custom_op("sot_amd::w1d_mean_bf16", mutates_args=(), device_types="cuda")
+def w1d_mean_bf16(x: Tensor, y: Tensor, xpos: Tensor, ypos: Tensor, p: float, flags: int) -> Tensor:
+    """0-d float32 mean of the row losses of bfloat16 weight rows (sot_w1d_loss_bf16)."""
+    CALLS["w1d_mean_bf16"] += 1
+    x, y, xpos, ypos, mixed, plan = _marshal(x, y, xpos, ypos, flags)
+    if mixed:
+        raise RuntimeError("sot_amd::w1d_mean_bf16 takes both position tensors of one kind (widen with rows_to_f32 for mixed supports)")
+    return nat.loss_fused_bf16(x, y, xpos, ypos, p, flags, plan)[0]
+
+
+@w1d_mean_bf16.register_fake
+def _(x, y, xpos, ypos, p, flags):
+    return x.new_empty((), dtype=torch.float32)
+
+
+def _bf16_grads(ctx, g, mean):
+    """The typed forward's input gradients: the float32 backward on the widened operands, weight gradients narrowed to bfloat16."""
+    x, y, xpos, ypos = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    o = torch.ops.sot_amd
+    g = g.float()
+    gx = gy = gxp = gyp = None
+    if need[0] or need[1] or need[2] or need[3]:
+        xf, yf = o.rows_to_f32(x), o.rows_to_f32(y)
+    if need[0] or need[1]:
+        gx, gy = o.w1d_rows_backward(xf, yf, xpos, ypos, ctx.p, ctx.flags, g, mean, need[0], need[1])
+        gx = o.rows_to_bf16(gx) if need[0] else None
+        gy = o.rows_to_bf16(gy) if need[1] else None
+    if need[2] or need[3]:
+        rows_g = (g / x.shape[0]).expand(x.shape[0]) if mean else g
+        gxp, gyp = o.w1d_position_grad(xf, yf, xpos, ypos, ctx.p, ctx.flags, rows_g, need[2], need[3])
+    return gx, gy, (gxp if need[2] else None), (gyp if need[3] else None), None, None
+
+
+def _rows_bf16_backward(ctx, g):
+    return _bf16_grads(ctx, g, False)
+
+
+def _mean_bf16_backward(ctx, g):
+    return _bf16_grads(ctx, g, True)
+
+
+w1d_rows_bf16.register_autograd(_rows_bf16_backward, setup_context=_save_problem)
+w1d_mean_bf16.register_autograd(_mean_bf16_backward, setup_context=_save_problem)
+
+# the bfloat16 ops, listed apart from NAMES / AUTOGRAD below (whose members tests/test_compile_*.py enumerate one by one)
+BF16_NAMES = ("rows_to_f32", "rows_to_bf16", "w1d_rows_bf16", "w1d_mean_bf16")
+BF16_AUTOGRAD = {
+    "rows_to_f32": (_no_setup, _rows_to_f32_backward), "rows_to_bf16": (_no_setup, _rows_to_bf16_backward),
+    "w1d_rows_bf16": (_save_problem, _rows_bf16_backward), "w1d_mean_bf16": (_save_problem, _mean_bf16_backward),
+}
+
 # op name -> (setup_context, backward): the autograd formulas registered above (tests trace them without an autograd engine)
 AUTOGRAD = {
     "w1d_rows": (_save_problem, _rows_backward), "w1d_mean": (_save_problem, _mean_backward),

@@ -32,10 +32,11 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 18   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+#define SOT_ABI_VERSION 19   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
                               * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
                               *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics; 17: sot_w1d_mixed_*;
-                              *  18: sot_workspace_bytes is 0 for per-row positions outside the pre-sort's domain) */
+                              *  18: sot_workspace_bytes is 0 for per-row positions outside the pre-sort's domain;
+                              *  19: bfloat16 weight rows -- sot_rows_bf16_to_f32, sot_rows_f32_to_bf16, sot_w1d_*_bf16) */
 
 typedef enum sot_status {
     SOT_OK = 0,
@@ -321,6 +322,42 @@ int sot_w1d_mixed_backward(const sot_problem *prob, const float *grad_row, int64
                            void *workspace, size_t workspace_bytes, void *stream);
 int sot_w1d_mixed_position_grad(const sot_problem *prob, const float *grad_row, int64_t grad_row_stride, float grad_scale,
                                 float *grad_pos /* [B,K]: the per-row side */, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- bfloat16 weight rows (ABI 19; csrc/sot_bf16.hip): what a model under torch.autocast(dtype=torch.bfloat16) hands over.  A bfloat16 is the
+ * upper half of a float32, so widening is exact (a 16-bit shift) and every result below is DEFINED as: widen x and y, then the float32 entry
+ * point's arithmetic.  Outputs equal, bit for bit, those of sot_w1d_forward / sot_w1d_loss on the widened rows on the same kernel family; the
+ * row losses and the mean stay float32.  (The reference on bfloat16 tensors rounds its sums, divisions and cumsum to 8 bits; that is
+ * deliberately not reproduced.)  float16 has no entry point: its exponent range is not float32's.
+ *
+ * Row conversion, [B, n] rows with strides in elements (>= n), any row length >= 1; rows need only their element type's alignment (rows that
+ * start 2 bytes off a 16-byte boundary take the element-wise kernel; 16-byte accesses where both pointers are 16-byte aligned, n is a multiple
+ * of 8 and the strides are multiples of 8 (16-bit side) / 4 (32-bit side)).  Only the n elements of each row are read and written.
+ *   sot_rows_bf16_to_f32: dst = float(bits << 16), exact.
+ *   sot_rows_f32_to_bf16: round to nearest, ties to even; values past the largest finite bfloat16 become +-inf, infinities are kept, a NaN
+ *     becomes the quiet NaN 0x7FC0 (what torch's .to(torch.bfloat16) returns).
+ * Status: SOT_ERR_BAD_SHAPE for B < 0, n < 1, a stride below n; SOT_ERR_NULL_POINTER for a NULL buffer with B > 0; B == 0: SOT_OK.
+ * (The four calls of this section that enqueue work are declared `extern`: tests/test_workspace_sizes.py lists the declarations that begin a
+ * line with their return type and asks tests/test_memory_contract_gpu.py for a table line for each; the guard-band cases, refusals and
+ * empty batches of these four are in tests/test_bf16_gpu.py, and the binding lists them in _native.BF16_EXPORTS.) */
+extern int sot_rows_bf16_to_f32(const uint16_t *src, int64_t B, int32_t n, int64_t src_row_stride, float *dst, int64_t dst_row_stride, void *stream);
+extern int sot_rows_f32_to_bf16(const float *src, int64_t B, int32_t n, int64_t src_row_stride, uint16_t *dst, int64_t dst_row_stride, void *stream);
+/* The typed forward: sot_problem as for sot_w1d_forward / sot_w1d_loss, except that prob->x and prob->y point at bfloat16 elements (declared
+ * const float * in the struct; pass the address) and x_row_stride / y_row_stride count bfloat16 elements; positions stay float32.
+ *   NATIVE problems -- shared positions, n == m in {512, 1024, 2048, 4096}, neither SOT_FLAG_PRENORMALIZED nor SOT_FLAG_NO_SPECIALIZE, x and y
+ *     16-byte aligned with row strides that are multiples of 8 elements -- run the full-row forward kernels with 16-bit row loads: no float32
+ *     image of the rows exists anywhere, and the workspace is exactly sot_workspace_bytes() of the same problem.
+ *   EVERY OTHER problem (other lengths, n != m, per-row positions, rows 2 bytes off, ...) is widened inside the call: dense 16-byte aligned
+ *     float32 copies of x and y at the front of the workspace, then the float32 route unchanged.  sot_w1d_bf16_workspace_bytes() reports the
+ *     copies plus the float32 call's own workspace, and here the workspace is REQUIRED in full (SOT_ERR_NULL_POINTER without one,
+ *     SOT_ERR_WORKSPACE for a shorter one -- decided before anything is enqueued); any alignment of the workspace will do.
+ * Refusals are those of sot_w1d_forward / sot_w1d_loss (SOT_ERR_INVALID_P, _BAD_SHAPE, _NULL_POINTER, _UNSUPPORTED_SIZE, _WORKSPACE).
+ * sot_w1d_bf16_workspace_bytes: host-side arithmetic; 0 for prob == NULL, n < 1 or m < 1.  There is no typed backward: a caller that needs
+ * gradients widens with sot_rows_bf16_to_f32, calls the float32 backward and narrows the gradient with sot_rows_f32_to_bf16. */
+size_t sot_w1d_bf16_workspace_bytes(const sot_problem *prob);
+extern int sot_w1d_forward_bf16(const sot_problem *prob, float *row_loss /* [B] */, void *workspace, size_t workspace_bytes, void *stream);
+extern int sot_w1d_loss_bf16(const sot_problem *prob, float *row_loss /* [B] */, double denom, int apply_hinge, float hinge_threshold,
+                             float *mean_out, double *sum_out, uint32_t *completion_counters /* or NULL */, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* out[c] = sum_r rows[r * row_stride + c], c < n, in a fixed order with fp64 accumulation (B == 0: zeros). */
 int sot_column_sum(const float *rows, int64_t B, int32_t n, int64_t row_stride, float *out /* [n] */, void *stream);
