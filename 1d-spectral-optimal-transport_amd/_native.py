@@ -31,7 +31,7 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 19                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 20                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
 FIR_TILE = 1024                  # include/sot_hip.h: SOT_FIR_TILE (outputs per workgroup of the FIR kernel)
 FIR_MIN_TAPS, FIR_MAX_TAPS, FIR_MAX_SAMPLES = 3, 512, 1 << 20   # the FIR kernels' domain (include/sot_hip.h: sot_fir_same_forward)
@@ -82,6 +82,7 @@ EXPORTS = {
     "sot_w1d_loss": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_double, ctypes.c_int, ctypes.c_float, _vp, _vp,
                                     _vp, _vp, ctypes.c_size_t, _vp]),
     "sot_w1d_bf16_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SotProblem)]),
+    "sot_w1d_bf16_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SotProblem), ctypes.c_int, ctypes.c_int]),
     "sot_w1d_quantiles": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp,
                                          ctypes.c_size_t, _vp]),
     "sot_w1d_quantiles_backward": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -153,6 +154,17 @@ BF16_EXPORTS = {
                                          _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
+# bfloat16 training (ABI 20; `extern` in include/sot_hip.h for the same reason): the native predicate, the typed backward -- sot_w1d_backward's
+# signature with 16-bit gradients and the fix-up scalar `rescale` behind them -- and the typed training form (sot_w1d_loss_and_grad's signature).
+# Their guard-band cases, refusals and empty batches are in tests/test_bf16_train_gpu.py.
+BF16_TRAIN_EXPORTS = {
+    "sot_w1d_bf16_native": (ctypes.c_int, [ctypes.POINTER(SotProblem)]),
+    "sot_w1d_backward_bf16": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                             _vp]),
+    "sot_w1d_loss_and_grad_bf16": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, ctypes.c_double, _vp, _vp, ctypes.c_float, _vp, _vp, _vp,
+                                                  ctypes.c_size_t, _vp]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -179,7 +191,7 @@ def load(build_if_missing: bool = True):
         elif not os.path.exists(path):
             raise RuntimeError(f"{path} is missing")
         lib = ctypes.CDLL(path)
-        for name, (res, args) in (*EXPORTS.items(), *BF16_EXPORTS.items()):
+        for name, (res, args) in (*EXPORTS.items(), *BF16_EXPORTS.items(), *BF16_TRAIN_EXPORTS.items()):
             fn = getattr(lib, name)  # AttributeError here = ABI mismatch, reported loudly
             fn.restype = res
             fn.argtypes = args
@@ -555,6 +567,76 @@ def loss_fused_bf16(x, y, xpos, ypos, p, flags, plan=None, denom=None, hinge=Non
                                    ws.numel() if ws is not None else 0, stream_ptr(dev))
     check(rc, p)
     return mean, row_loss
+
+
+# ---- bfloat16 training (ABI 20): 16-bit gradients out of the backward kernels.  Each gradient element is the float32 call's element on
+# x.float(), y.float(), rounded once to nearest even; row losses and the mean are the float32 call's bits.
+
+def bf16_native(x, y, xpos, ypos, p, flags, plan=None) -> bool:
+    """Does the typed backward / training form run its native kernels on these rows (sot_w1d_bf16_native: host arithmetic on shapes, strides,
+    flags and the alignment of the two weight pointers -- no device is touched, so CPU or meta stand-ins answer too)?  x, y: 2-D weight rows
+    as the native calls take them; positions: 1-D when shared."""
+    pr = SotProblem()
+    pr.B, pr.n, pr.m = x.shape[0], x.shape[1], y.shape[1]
+    pr.x_row_stride = x.stride(0) if pr.B > 1 else pr.n
+    pr.y_row_stride = y.stride(0) if pr.B > 1 else pr.m
+    pr.xpos_row_stride = 0 if (plan is not None or xpos.ndim == 1) else pr.n
+    pr.ypos_row_stride = 0 if (plan is not None or ypos.ndim == 1) else pr.m
+    pr.x, pr.y = x.data_ptr(), y.data_ptr()
+    pr.p, pr.flags = float(p), int(flags)
+    return bool(load().sot_w1d_bf16_native(ctypes.byref(pr)))
+
+
+def _bf16_backward_workspace(pr: SotProblem, device, need_gx, need_gy):
+    nbytes = int(load().sot_w1d_bf16_backward_workspace_bytes(ctypes.byref(pr), int(need_gx), int(need_gy)))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes > 0 else None
+
+
+def backward_rows_bf16(x, y, xpos, ypos, p, flags, grad_row, need_gx=True, need_gy=True, plan=None, grad_scale=1.0, rescale=None, gy_out=None):
+    """backward_rows for bfloat16 weights: (gx, gy) in bfloat16 (sot_w1d_backward_bf16).  grad_row: float32, [B] or one broadcast element, or
+    None (1 for every row).  rescale (one-element float32 device tensor, y-only calls) with gy_out: the fix-up mode -- gy_out is rewritten with
+    rne(gradient * rescale), or left as it is when rescale is exactly 1."""
+    lib = load()
+    _require_bf16_rows(x, y, xpos, ypos)
+    dev = x.device
+    B, n = x.shape
+    m = y.shape[1]
+    gx = torch.empty(B, n, dtype=torch.bfloat16, device=dev) if need_gx else None
+    gy = (gy_out if gy_out is not None else torch.empty(B, m, dtype=torch.bfloat16, device=dev)) if need_gy else None
+    if gy_out is not None and (gy_out.dtype != torch.bfloat16 or tuple(gy_out.shape) != (B, m) or not gy_out.is_contiguous()):
+        raise RuntimeError("gy_out must be a contiguous bfloat16 [B, m] tensor")
+    if rescale is not None and (need_gx or rescale.dtype != torch.float32 or rescale.numel() != 1 or not rescale.is_cuda):
+        raise RuntimeError("rescale is a one-element float32 device tensor of a y-only call")
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = _bf16_backward_workspace(pr, dev, need_gx, need_gy)
+    g = grad_row.contiguous() if grad_row is not None else None
+    stride = 0 if (g is None or g.numel() == 1) else 1
+    if stride == 1 and g.numel() != B:
+        raise RuntimeError(f"grad_row has {g.numel()} elements for {B} rows")
+    with _on_device(dev):
+        rc = lib.sot_w1d_backward_bf16(ctypes.byref(pr), _ptr(g), stride, float(grad_scale), _ptr(gx), _ptr(gy), _ptr(rescale), _ptr(ws),
+                                       ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return gx, gy
+
+
+def loss_and_grad_bf16(x, y, xpos, ypos, p, flags, plan=None, fused_mean=None):
+    """Training form for bfloat16 weights (sot_w1d_loss_and_grad_bf16): (mean 0-d float32, row_loss [B] float32, d mean / d y [B, m] bfloat16)."""
+    lib = load()
+    _require_bf16_rows(x, y, xpos, ypos)
+    dev = x.device
+    B, m = x.shape[0], y.shape[1]
+    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    gy = torch.empty(B, m, dtype=torch.bfloat16, device=dev)
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = _bf16_backward_workspace(pr, dev, False, True)
+    with _on_device(dev):
+        rc = lib.sot_w1d_loss_and_grad_bf16(ctypes.byref(pr), row_loss.data_ptr(), float(B), mean.data_ptr(), None, 1.0 / B, gy.data_ptr(),
+                                            completion_counters(dev) if _want_tail(fused_mean) else None,
+                                            _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return mean, row_loss, gy
 
 
 def prepared_loss_call(x, y, xpos, ypos, p, flags, plan, row_out, mean_out, sum_out=None, stream=None):

@@ -11,14 +11,8 @@ namespace sot {
 // Row conversion.  A workgroup of 256 threads walks groups of `rpg` rows (as many short rows as its threads cover in one pass); a thread
 // owns chunks of CH consecutive elements: CH = 8 -- one 16-byte access on the 16-bit side, two on the 32-bit side -- where both pointers,
 // both strides and the length allow, CH = 1 (element-wise: rows that start 2 bytes off a boundary, odd lengths) otherwise.
+// (f32_to_bf16_rne: sot_full_common.hpp)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f)
-{
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)0x7FC0;      // NaN stays NaN (the payload is not kept)
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);       // ties to even; past the largest finite value: the carry makes +-inf
-}
-
 template <int CH>
 __global__ __launch_bounds__(256) void sot_rows_bf16_to_f32_kernel(const uint16_t* __restrict__ src, int64_t B, int n, int64_t ss,
                                                                    float* __restrict__ dst, int64_t ds, int cpr, int rpg)
@@ -141,7 +135,7 @@ static hipError_t dispatch_forward_full_bf16(int pm, const FwdArgs& a, hipStream
 // The native route's condition (host side; sot_w1d_bf16_workspace_bytes reports by the same predicate): shared positions, n == m in the
 // set above, kernels with the length at compile time allowed, weights normalised by the call, rows of x and y on 16-byte boundaries
 // (pointer 16-byte aligned, row strides multiples of 8 elements).
-static inline bool bf16_native(const sot_problem* pr)
+bool bf16_native(const sot_problem* pr)
 {
     return pr->xpos_row_stride == 0 && pr->ypos_row_stride == 0 && pr->n == pr->m &&
            (pr->n == 512 || pr->n == 1024 || pr->n == 2048 || pr->n == 4096) &&

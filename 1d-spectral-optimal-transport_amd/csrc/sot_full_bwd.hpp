@@ -23,6 +23,27 @@ __device__ __forceinline__ void lds_store(uint32_t addr, float v)
     *reinterpret_cast<__attribute__((address_space(3))) float*>((uintptr_t)addr) = v;
 }
 
+// The 16-bit gradient stores of a thread that owns CPT = 8 contiguous elements of a row that fills its geometry (GT = uint16_t): dst = the
+// address of the thread's first element in the gradient row (16-byte aligned: the host guarantees 16-byte aligned rows of N elements).
+// Identity permutation: one 16-byte store; otherwise single 16-bit elements through the plan's permutation (perm = its entries for e0 ...).
+template <int CPT>
+__device__ __forceinline__ void store_grad_row_bf16(uint16_t* dst, const float (&o)[CPT], bool ident, const int* perm, int e0)
+{
+    static_assert(CPT == 8, "8 bfloat16 gradients = one 16-byte store");
+    if (ident) {
+        uint4 v;
+        v.x = (uint32_t)f32_to_bf16_rne(o[0]) | ((uint32_t)f32_to_bf16_rne(o[1]) << 16);
+        v.y = (uint32_t)f32_to_bf16_rne(o[2]) | ((uint32_t)f32_to_bf16_rne(o[3]) << 16);
+        v.z = (uint32_t)f32_to_bf16_rne(o[4]) | ((uint32_t)f32_to_bf16_rne(o[5]) << 16);
+        v.w = (uint32_t)f32_to_bf16_rne(o[6]) | ((uint32_t)f32_to_bf16_rne(o[7]) << 16);
+        *reinterpret_cast<uint4*>(dst) = v;
+    } else {
+        uint16_t* const row = dst - e0;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) row[perm[k]] = f32_to_bf16_rne(o[k]);
+    }
+}
+
 // Gradient rows of the one-sided spectra (129 / 257 / 513 / 1025 / 2049 bins: rows of 4 N bytes, never a multiple of 16) leave the
 // kernel through LDS (round 4).  Before: every thread stored its CPT contiguous gradients one dword at a time, i.e. CPT store
 // instructions per wave at a lane stride of 4 CPT bytes, each touching every 128-B line of the wave's span partially.  The L2 answered
@@ -69,9 +90,19 @@ __device__ __forceinline__ void flush_row_grad(const float* lds_row, float* grow
 // smaller region buys another resident row: 2048-bin rows, two per workgroup (79.7 us).
 // MINB: second argument of __launch_bounds__ = waves per SIMD the kernel is compiled for (HIP's meaning; 4 -> at most 128 VGPRs, which
 // for these 256-thread workgroups is four workgroups per CU), 1 = no constraint.
-template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX = 0, bool WANT_X = true, bool SLIM = false, int MINB = 1, bool RP = false>
+// WT (sot_full_common.hpp: fetch_row): the element type of the weight rows in memory -- float, or uint16_t for bfloat16 rows (a.x / a.y then
+// point at 16-bit elements and the row strides count them; instantiated by sot_bf16_bwd.hip).  GT: the element type of the gradient rows
+// b.gx / b.gy -- float, or uint16_t for bfloat16 gradients: ox[k] / oy[k] stay the float32 values of the float32 kernel and are rounded once,
+// to nearest even, at the store (b.gx / b.gy then point at 16-bit elements, rows of N of them on 16-byte boundaries).  The y-only 16-bit kernel
+// also has the FIX-UP mode of BwdArgs::rescale: every workgroup reads the scalar first and returns at once when it is exactly 1 (what
+// sot_scale_inplace does); otherwise the stored element is rne(oy[k] * *rescale), one float32 multiply in front of the one rounding.
+template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX = 0, bool WANT_X = true, bool SLIM = false, int MINB = 1, bool RP = false,
+          class WT = float, class GT = float>
 __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const BwdArgs b)
 {
+    constexpr bool G16 = !std::is_same<GT, float>::value;
+    static_assert(std::is_same<WT, float>::value || (NX == 0 && !RP), "16-bit rows: rows that fill their geometry, shared positions");
+    static_assert(!G16 || (std::is_same<GT, uint16_t>::value && NX == 0 && !RP), "16-bit gradients: bfloat16, rows that fill their geometry, shared positions");
     static_assert(!RP || (ROWS == 1 && NX == 0 && CPT == 8), "per-row positions (see sot_forward_full_kernel): one row per workgroup, rows that fill the 8-element geometry");
     static_assert(!(SLIM && WANT_X), "SLIM is a y-only layout");
     constexpr int GR = SLIM ? 2 : 1;
@@ -81,6 +112,16 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
     constexpr bool WITH_LOSS = !WANT_X;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const FwdArgs& a = b.f;
+    float rescale = 1.0f;
+    bool rescaled = false;   // kernel-uniform
+    if constexpr (G16 && !WANT_X) {
+        if (b.rescale != nullptr) {
+            rescale = *b.rescale;
+            if (rescale == 1.0f) return;   // the gradient in place is already the answer (every thread of every workgroup leaves: no barrier is pending)
+            rescaled = true;
+        }
+    }
+    (void)rescale; (void)rescaled;
     const int64_t row_step = (int64_t)gridDim.x * ROWS;
     int64_t row0 = (int64_t)blockIdx.x * ROWS;
     float rx[CPT], ry[CPT];
@@ -95,7 +136,7 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
     double* const wtot = c.wtot;
     if (row0 < a.B) {
         const int64_t r = min(row0 + rg, a.B - 1);
-        fetch_row<G, CPT, NX>(a.x + r * a.xs, a.y + r * a.ys, t, a.n, rx, ry);
+        fetch_row<G, CPT, NX, WT>(weight_row<WT>(a.x, r, a.xs), weight_row<WT>(a.y, r, a.ys), t, a.n, rx, ry);
     }
 
 #ifdef SOT_STAMPS
@@ -136,8 +177,9 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
         }
         int ix[RP ? CPT : 1] = {}, iy[RP ? CPT : 1] = {}, psx[RP ? CPT : 1] = {}, psy[RP ? CPT : 1] = {};
         if constexpr (RP) rowpos_row_setup<G, CPT, ROWS, GR, NX>(a, c, rowc, ix, iy, psx, psy);
-        full_build_cdfs<G, CPT, ROWS, GR, SQ, NX>(a, c, rx, ry, more ? a.x + rn * a.xs : nullptr,
-                                                  more ? a.y + rn * a.ys : nullptr, wx, wy, Sx, Sy, cu, cv, sacc, RP ? psx : nullptr, RP ? psy : nullptr);
+        full_build_cdfs<G, CPT, ROWS, GR, SQ, NX, true, true, false, NoRowHook, WT>(
+            a, c, rx, ry, more ? weight_row<WT>(a.x, rn, a.xs) : nullptr, more ? weight_row<WT>(a.y, rn, a.ys) : nullptr, wx, wy, Sx, Sy, cu, cv, sacc,
+            RP ? psx : nullptr, RP ? psy : nullptr);
         SOT_PH(sacc, 9);   // wave totals, CDF values to LDS, next row's loads issued, barrier
 
         // ---- merge walk over (pad zero levels ++ U, V), exactly E steps per thread.  The gradient of a level is known one
@@ -339,7 +381,19 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
                     for (int k = 0; k < CPT; ++k) { if (e0 + k < N) gs[e0 + k] = oy[k]; }
                 }
             }
-            if (WANT_X && b.gx && !stage_x) {
+            if constexpr (G16) {   // bfloat16 gradient rows: rounded at the store, 8 contiguous gradients as one 16-byte store
+                if constexpr (WANT_X) {
+                    if (b.gx) store_grad_row_bf16<CPT>(reinterpret_cast<uint16_t*>(b.gx) + row * (int64_t)N + e0, ox, c.x_ident, a.xperm + e0, e0);
+                }
+                if (b.gy) {
+                    if (rescaled) {
+#pragma unroll
+                        for (int k = 0; k < CPT; ++k) oy[k] = oy[k] * rescale;
+                    }
+                    store_grad_row_bf16<CPT>(reinterpret_cast<uint16_t*>(b.gy) + row * (int64_t)N + e0, oy, c.y_ident, a.yperm + e0, e0);
+                }
+            }
+            if (!G16 && WANT_X && b.gx && !stage_x) {
                 float* dst = b.gx + row * (int64_t)nreal;
                 if (Geo::ALIGNED && c.x_ident) {
 #pragma unroll
@@ -356,7 +410,7 @@ __global__ __launch_bounds__(ROWS * G, MINB) void sot_backward_full_kernel(const
                     }
                 }
             }
-            if (b.gy && !stage_y) {
+            if (!G16 && b.gy && !stage_y) {
                 float* dst = b.gy + row * (int64_t)nreal;
                 if (Geo::ALIGNED && c.y_ident) {
 #pragma unroll
@@ -556,40 +610,42 @@ static hipError_t dispatch_area_train_g(const BwdArgs& b, hipStream_t s)
     return (b.f.flags & SOT_FLAG_SQUARE) ? launch_area_train<G, CPT, ROWS, true, NX>(b, s) : launch_area_train<G, CPT, ROWS, false, NX>(b, s);
 }
 
-template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool WANT_X, bool SLIM = false, int MINB = 1, bool RP = false>
+// WT / GT (here and below): the weight and gradient element types of sot_backward_full_kernel; same LDS layout, block and row groups whatever they are
+template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool WANT_X, bool SLIM = false, int MINB = 1, bool RP = false,
+          class WT = float, class GT = float>
 static hipError_t launch_backward_full_x(const BwdArgs& b, hipStream_t s)
 {
     constexpr FullLayout L = full_layout<G, CPT, ROWS, SLIM ? 2 : 1, NX>();
-    return launch_persistent_profiled<sot_backward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, WANT_X, SLIM, MINB, RP>>(
+    return launch_persistent_profiled<sot_backward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, WANT_X, SLIM, MINB, RP, WT, GT>>(
         b, sizeof(float) * (size_t)L.total, (b.f.B + ROWS - 1) / ROWS, ROWS * G, s);
 }
 
 // WHICH: bit 0 = the both-gradient kernels, bit 1 = the y-only kernels of this layout (a geometry whose y-only calls go to
 // dispatch_backward_full_y instantiates only the former)
-template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, int WHICH = 3>
+template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, int WHICH = 3, class WT = float, class GT = float>
 static hipError_t launch_backward_full(const BwdArgs& b, hipStream_t s)
 {
     // in dont_normalize mode the y side's mass term lands in the x side's gradient, which needs gx anyway
-    if constexpr (WHICH & 1) { if (b.gx != nullptr) return launch_backward_full_x<G, CPT, ROWS, PM, LIM, SQ, NX, true>(b, s); }
-    if constexpr (WHICH & 2) { if (b.gx == nullptr) return launch_backward_full_x<G, CPT, ROWS, PM, LIM, SQ, NX, false>(b, s); }
+    if constexpr (WHICH & 1) { if (b.gx != nullptr) return launch_backward_full_x<G, CPT, ROWS, PM, LIM, SQ, NX, true, false, 1, false, WT, GT>(b, s); }
+    if constexpr (WHICH & 2) { if (b.gx == nullptr) return launch_backward_full_x<G, CPT, ROWS, PM, LIM, SQ, NX, false, false, 1, false, WT, GT>(b, s); }
     return hipErrorInvalidConfiguration;
 }
 
-template <int G, int CPT, int ROWS, int NX = 0, int WHICH = 3>
+template <int G, int CPT, int ROWS, int NX = 0, int WHICH = 3, class WT = float, class GT = float>
 static hipError_t dispatch_backward_full_g(int pm, const BwdArgs& b, hipStream_t s)
 {
     static_assert(sizeof(float) * (size_t)full_layout<G, CPT, ROWS, true, NX>().total <= kLdsLimit, "workgroup fits one CU's LDS");
-    return with_mode(pm, b.f.flags, [&](auto md) { using M = decltype(md); return launch_backward_full<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX, WHICH>(b, s); });
+    return with_mode(pm, b.f.flags, [&](auto md) { using M = decltype(md); return launch_backward_full<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX, WHICH, WT, GT>(b, s); });
 }
 
 // the y-only kernels of one geometry alone (gx == nullptr)
-template <int G, int CPT, int ROWS, int NX = 0, bool SLIM = true, int MINB = 1>
+template <int G, int CPT, int ROWS, int NX = 0, bool SLIM = true, int MINB = 1, class WT = float, class GT = float>
 static hipError_t dispatch_backward_full_y(int pm, const BwdArgs& b, hipStream_t s)
 {
     static_assert(sizeof(float) * (size_t)full_layout<G, CPT, ROWS, SLIM ? 2 : 1, NX>().total <= kLdsLimit, "workgroup fits one CU's LDS");
     return with_mode(pm, b.f.flags, [&](auto md) {
         using M = decltype(md);
-        return launch_backward_full_x<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX, false, SLIM, MINB>(b, s);
+        return launch_backward_full_x<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX, false, SLIM, MINB, false, WT, GT>(b, s);
     });
 }
 

@@ -155,6 +155,15 @@ __device__ __forceinline__ const float* weight_row(const float* base, int64_t r,
     else return reinterpret_cast<const float*>(reinterpret_cast<const WT*>(base) + r * stride);
 }
 
+// float32 -> bfloat16, round to nearest even: the one narrowing of the library (the row-conversion kernel of sot_bf16.hip and the 16-bit
+// gradient stores of sot_full_bwd.hpp), the bits of torch's .to(torch.bfloat16).
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)0x7FC0;      // NaN stays NaN (the payload is not kept)
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);       // ties to even; past the largest finite value: the carry makes +-inf
+}
+
 template <int G, int CPT>
 __device__ __forceinline__ void fetch_full_row(const float* __restrict__ x, const float* __restrict__ y, int t, float (&rx)[CPT],
                                                float (&ry)[CPT])

@@ -176,6 +176,10 @@ int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, fl
 int run_backward(const sot_problem* pr, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* gx, float* gy,
                  void* workspace, size_t workspace_bytes, void* stream, float* row_loss_out = nullptr, bool* fused = nullptr,
                  const MeanTail* mean_tail = nullptr);
+// sot_bf16.hip (bfloat16 rows): the row conversions and the native route's condition on the problem; sot_bf16_bwd.hip: the typed backward
+int launch_rows_bf16_to_f32(const uint16_t* src, int64_t B, int n, int64_t ss, float* dst, int64_t ds, hipStream_t s);
+int launch_rows_f32_to_bf16(const float* src, int64_t B, int n, int64_t ss, uint16_t* dst, int64_t ds, hipStream_t s);
+bool bf16_native(const sot_problem* pr);
 // sot_csr.hip
 int run_forward_csr(const float* xw, const float* xp, const int64_t* xoff, int64_t x_nnz, const float* yw, const float* yp,
                     const int64_t* yoff, int64_t y_nnz, int64_t B, int max_n, int max_m, float p, uint32_t flags, float* row_loss,

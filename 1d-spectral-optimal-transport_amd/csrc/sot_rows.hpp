@@ -929,6 +929,7 @@ struct BwdArgs {
     int64_t grad_row_stride;
     float grad_scale;          // multiplies every upstream gradient (1/B of the batch mean)
     float* gx; float* gy;
+    const float* rescale;      // the 16-bit y-only full-row kernel alone (sot_full_bwd.hpp: fix-up mode): device scalar or null
 };
 
 template <int G, int CPT, bool ROWPOS, int PM, bool LIM, bool VEC>

@@ -9,8 +9,9 @@ Same names, argument meaning and error behaviour as the reference's ``losses`` m
 
 All arithmetic on float32 HIP-device tensors runs in the hand-written HIP library (csrc/, C ABI in
 include/sot_hip.h); this file only reshapes, marshals pointers and wires autograd.  bfloat16 weights on the device (autocast) are
-the float32 call on the exactly widened rows: the typed forward where no gradient is asked for, a widening kernel in front of the
-float32 path -- and a narrowing one behind its gradient -- where one is (_hip_domain).  Tensors outside the library's domain
+the float32 call on the exactly widened rows: the typed forward where no gradient is asked for; where one is, the typed backward and
+training form on the rows that have 16-bit backward kernels (_typed_training_applies), a widening kernel in front of the float32 path
+-- and a narrowing one behind its gradient -- elsewhere (_hip_domain).  Tensors outside the library's domain
 -- CPU tensors, float64 -- take the reference's own route, torch ops (_torch_path.py), because the reference is device- and
 dtype-agnostic (losses.py:129-211) and `accelerator: cpu` has to keep working.
 """
@@ -95,11 +96,32 @@ def _widen(t):
 def _typed_forward_applies(x, y, xpos, ypos, return_quantiles=False) -> bool:
     """bfloat16 weights: does the call take the typed forward (sot_w1d_forward_bf16 / sot_w1d_loss_bf16 -- 16-bit row loads in the kernel on
     the headline and paper shapes, widening inside the call elsewhere)?  Calls that need no gradient do: torch.no_grad, inference_mode,
-    operands without requires_grad.  Calls that need one, return_quantiles and the mixed-supports route widen x and y first (_widen) and
-    follow the float32 path unchanged."""
+    operands without requires_grad.  Calls that need one take the typed training calls where _typed_training_applies holds; the others,
+    return_quantiles and the mixed-supports route widen x and y first (_widen) and follow the float32 path unchanged."""
     if return_quantiles or mixed_route_applies(x, y, xpos, ypos):
         return False
     return not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)))
+
+
+def _typed_training_applies(x, y, xpos, ypos, return_quantiles=False, flags=0, p=1.0) -> bool:
+    """bfloat16 weights that ask for a gradient: does the call take the typed backward / training form (sot_w1d_backward_bf16 /
+    sot_w1d_loss_and_grad_bf16 -- 16-bit row loads and 16-bit gradient stores inside the backward kernels, no float32 image of a spectrum or
+    of a gradient)?  It does when x or y requires a gradient and neither position tensor does, outside return_quantiles, the mixed-supports
+    route and compiled calls, on the problems those kernels exist for (nat.bf16_native: shared positions, 512 / 1024 / 2048 / 4096 bins,
+    16-byte aligned rows, not the opt-in tie-free form).  Everything else keeps the _widen route: there the C call would widen on the forward
+    AND on the backward, two conversions more than _widen's.  A function of dtypes, shapes, strides, requires_grad, the grad mode, the flag
+    word and the alignment of the two data pointers: no device is touched."""
+    if _compiling() or x.dtype is not torch.bfloat16 or y.dtype is not torch.bfloat16 or not torch.is_grad_enabled():
+        return False
+    if not (x.requires_grad or y.requires_grad) or xpos.requires_grad or ypos.requires_grad:
+        return False
+    if return_quantiles or xpos.ndim != 1 or ypos.ndim != 1 or mixed_route_applies(x, y, xpos, ypos):
+        return False
+    if x.ndim < 2 or y.ndim < 2 or x.shape[-1] != xpos.shape[0] or y.shape[-1] != ypos.shape[0]:
+        return False    # (the general path says what is wrong with such a call)
+    x2 = nat.rows_view(x.detach().reshape(-1, x.shape[-1]))   # the rows as _marshal hands them to the native call
+    y2 = nat.rows_view(y.detach().reshape(-1, y.shape[-1]))
+    return nat.bf16_native(x2, y2, xpos, ypos, p, flags)
 
 
 ROW_SIDE_LIMIT = 16384    # points of ONE side (csrc/sot_launch.hpp pick_cfg: at most 1024 threads x 16 points per row)
@@ -204,6 +226,25 @@ class _RowLoss(torch.autograd.Function):
             gxp, gyp = _position_grads(x, y, xpos, ypos, ctx.p, ctx.flags, ctx.plan, grad_rows.float(), ctx.needs_input_grad[2],
                                        ctx.needs_input_grad[3], perm_in=perm)
         return gx, gy, gxp, gyp, None, None, None
+
+
+class _RowLossBF16(torch.autograd.Function):
+    """_RowLoss for bfloat16 weights where _typed_training_applies holds (shared positions that ask for no gradient): the typed forward, and
+    the typed backward with the row cotangents -- the float32 node's arguments, each gradient element its float32 element rounded once."""
+
+    @staticmethod
+    def forward(ctx, x, y, xpos, ypos, p, flags, plan):
+        rows = nat.forward_rows_bf16(x, y, xpos, ypos, p, flags, plan)
+        ctx.save_for_backward(x, y, xpos, ypos)
+        ctx.p, ctx.flags, ctx.plan = p, flags, plan
+        return rows
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        x, y, xpos, ypos = ctx.saved_tensors
+        gx, gy = nat.backward_rows_bf16(x, y, xpos, ypos, ctx.p, ctx.flags, grad_rows.float(), need_gx=ctx.needs_input_grad[0],
+                                        need_gy=ctx.needs_input_grad[1], plan=ctx.plan)
+        return gx, gy, None, None, None, None, None
 
 
 MIXED_ROUTE = True   # module switch (tests and tools/bench_mixed.py compare both routes): False = mixed supports are materialised as before
@@ -373,6 +414,39 @@ class _FusedMeanLoss(torch.autograd.Function):
             gx, gy = nat.backward_rows(x, y, xpos, ypos, ctx.p, ctx.flags, g.float(), need_gx=ctx.needs_input_grad[0],
                                        need_gy=ctx.needs_input_grad[1], plan=ctx.plan, grad_scale=1.0 / x.shape[0])
         return gx, gy, gxp, gyp, None, None, None
+
+
+class _FusedMeanLossBF16(torch.autograd.Function):
+    """_FusedMeanLoss for bfloat16 weights where _typed_training_applies holds.  The training step (only y asks for a gradient) is ONE node on
+    16-bit data: its forward is sot_w1d_loss_and_grad_bf16, which stores d mean / d y in bfloat16 before the upstream gradient is known; its
+    backward calls the typed backward in fix-up mode on that buffer with the upstream scalar -- an empty launch for a plain loss.backward(),
+    a recomputation into the buffer for a weighted loss -- which returns the float32 node's bits rounded once: rne(early gradient * upstream).
+    Otherwise (x differentiated, EARLY_GRADIENT off, a second backward through a retained graph): the typed forward + mean, and the typed
+    backward with the float32 node's late arguments."""
+
+    @staticmethod
+    def forward(ctx, x, y, xpos, ypos, p, flags, plan):
+        ctx.p, ctx.flags, ctx.plan = p, flags, plan
+        ctx.early_gy = None
+        if ctx.needs_input_grad[1] and not ctx.needs_input_grad[0] and EARLY_GRADIENT:
+            mean, _, ctx.early_gy = nat.loss_and_grad_bf16(x, y, xpos, ypos, p, flags, plan)
+        else:
+            mean, _ = nat.loss_fused_bf16(x, y, xpos, ypos, p, flags, plan)
+        ctx.save_for_backward(x, y, xpos, ypos)
+        return mean
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, xpos, ypos = ctx.saved_tensors
+        scale = 1.0 / x.shape[0]
+        if ctx.early_gy is not None:   # consumed once, as in _FusedMeanLoss
+            gy, ctx.early_gy = ctx.early_gy, None
+            nat.backward_rows_bf16(x, y, xpos, ypos, ctx.p, ctx.flags, None, need_gx=False, need_gy=True, plan=ctx.plan, grad_scale=scale,
+                                   rescale=g.float().reshape(1), gy_out=gy)
+            return None, gy, None, None, None, None, None
+        gx, gy = nat.backward_rows_bf16(x, y, xpos, ypos, ctx.p, ctx.flags, g.float(), need_gx=ctx.needs_input_grad[0],
+                                        need_gy=ctx.needs_input_grad[1], plan=ctx.plan, grad_scale=scale)
+        return gx, gy, None, None, None, None, None
 
 
 class _RowMean(torch.autograd.Function):
@@ -644,13 +718,16 @@ class Wasserstein1D(torch.nn.Module):
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
         if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
             return self._torch_forward(x, y, x_pos_, y_pos_, kwargs, rows_only=True)
-        if x.dtype is torch.bfloat16 and not _typed_forward_applies(x, y, x_pos_, y_pos_):
+        if x.dtype is torch.bfloat16 and not (_typed_forward_applies(x, y, x_pos_, y_pos_)
+                                              or _typed_training_applies(x, y, x_pos_, y_pos_, False, self._flag_word(kwargs), self.p)):
             x, y = _widen(x), _widen(y)
         if mixed_route_applies(x, y, x_pos_, y_pos_):   # a shared grid against per-row positions: nothing is materialised
             loss = _mixed_row_losses(x, y, x_pos_, y_pos_, self.p, self._flag_word(kwargs), self._plans)
         else:
             x, y, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
-            if x.dtype is torch.bfloat16:   # no gradient asked for: the typed forward
+            if x.dtype is torch.bfloat16 and not _compiling() and torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+                loss = _RowLossBF16.apply(x, y, x_pos_, y_pos_, float(self.p), flags, plan)   # (_typed_training_applies held)
+            elif x.dtype is torch.bfloat16:   # no gradient asked for: the typed forward
                 loss = (_o.w1d_rows_bf16(x, y, x_pos_, y_pos_, float(self.p), flags) if _compiling()
                         else nat.forward_rows_bf16(x, y, x_pos_, y_pos_, float(self.p), flags, plan))
             elif _compiling():
@@ -702,8 +779,10 @@ class Wasserstein1D(torch.nn.Module):
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
         if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
             return self._torch_forward(x, y, x_pos_, y_pos_, kwargs)
-        if x.dtype is torch.bfloat16 and not _typed_forward_applies(x, y, x_pos_, y_pos_, kwargs.get("return_quantiles", False)):
-            x, y = _widen(x), _widen(y)   # a gradient is asked for (or quantiles, mixed supports): the float32 path, gradients narrowed
+        if x.dtype is torch.bfloat16:
+            rq = kwargs.get("return_quantiles", False)
+            if not (_typed_forward_applies(x, y, x_pos_, y_pos_, rq) or _typed_training_applies(x, y, x_pos_, y_pos_, rq, self._flag_word(kwargs), self.p)):
+                x, y = _widen(x), _widen(y)   # quantiles, mixed supports, position gradients, rows without 16-bit backward kernels: the float32 path, gradients narrowed
         return self._hip_forward(x, y, x_pos, y_pos, x_pos_, y_pos_, kwargs)
 
     def _hip_forward(self, x, y, x_pos, y_pos, x_pos_, y_pos_, kwargs):
@@ -718,9 +797,12 @@ class Wasserstein1D(torch.nn.Module):
             # default reduction: forward and the mean over every row (losses.py:211) in one native call
             x2, y2, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
             grad_on = torch.is_grad_enabled()
-            if x2.dtype is torch.bfloat16:   # no gradient asked for (forward): the typed forward + batch mean, one native call
+            if x2.dtype is torch.bfloat16:   # a gradient w.r.t. the weights on the typed route (_typed_training_applies held), or none asked for
                 if _compiling():
                     return _o.w1d_mean_bf16(x2, y2, x_pos_, y_pos_, float(self.p), flags)
+                if grad_on and (x2.requires_grad or y2.requires_grad):
+                    return _FusedMeanLossBF16.apply(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)
+                # the typed forward + batch mean, one native call
                 return nat.loss_fused_bf16(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)[0]
             if _compiling():   # the same two native calls as below, as ops: the training form when only y (and positions) ask for a gradient
                 if grad_on and EARLY_GRADIENT and y2.requires_grad and not x2.requires_grad:

@@ -32,11 +32,13 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 19   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+#define SOT_ABI_VERSION 20   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
                               * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
                               *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics; 17: sot_w1d_mixed_*;
                               *  18: sot_workspace_bytes is 0 for per-row positions outside the pre-sort's domain;
-                              *  19: bfloat16 weight rows -- sot_rows_bf16_to_f32, sot_rows_f32_to_bf16, sot_w1d_*_bf16) */
+                              *  19: bfloat16 weight rows -- sot_rows_bf16_to_f32, sot_rows_f32_to_bf16, sot_w1d_*_bf16;
+                              *  20: bfloat16 training -- sot_w1d_backward_bf16, sot_w1d_loss_and_grad_bf16, sot_w1d_bf16_native,
+                              *      sot_w1d_bf16_backward_workspace_bytes) */
 
 typedef enum sot_status {
     SOT_OK = 0,
@@ -351,13 +353,45 @@ extern int sot_rows_f32_to_bf16(const float *src, int64_t B, int32_t n, int64_t 
  *     copies plus the float32 call's own workspace, and here the workspace is REQUIRED in full (SOT_ERR_NULL_POINTER without one,
  *     SOT_ERR_WORKSPACE for a shorter one -- decided before anything is enqueued); any alignment of the workspace will do.
  * Refusals are those of sot_w1d_forward / sot_w1d_loss (SOT_ERR_INVALID_P, _BAD_SHAPE, _NULL_POINTER, _UNSUPPORTED_SIZE, _WORKSPACE).
- * sot_w1d_bf16_workspace_bytes: host-side arithmetic; 0 for prob == NULL, n < 1 or m < 1.  There is no typed backward: a caller that needs
- * gradients widens with sot_rows_bf16_to_f32, calls the float32 backward and narrows the gradient with sot_rows_f32_to_bf16. */
+ * sot_w1d_bf16_workspace_bytes: host-side arithmetic; 0 for prob == NULL, n < 1 or m < 1.  The typed backward and training form follow
+ * below (ABI 20). */
 size_t sot_w1d_bf16_workspace_bytes(const sot_problem *prob);
 extern int sot_w1d_forward_bf16(const sot_problem *prob, float *row_loss /* [B] */, void *workspace, size_t workspace_bytes, void *stream);
 extern int sot_w1d_loss_bf16(const sot_problem *prob, float *row_loss /* [B] */, double denom, int apply_hinge, float hinge_threshold,
                              float *mean_out, double *sum_out, uint32_t *completion_counters /* or NULL */, void *workspace,
                              size_t workspace_bytes, void *stream);
+
+/* ---- bfloat16 training (ABI 20; csrc/sot_bf16_bwd.hip): sot_w1d_backward and sot_w1d_loss_and_grad for bfloat16 weight rows AND bfloat16
+ * gradients.  prob as for the typed forward (x, y bfloat16, their strides in bfloat16 elements, positions float32); grad_x / grad_y are dense
+ * bfloat16 rows of n / m elements; grad_row, the row losses and the mean stay float32.
+ * DEFINED RESULT: every gradient element equals, bit for bit, rne(v) -- v the float32 element that sot_w1d_backward / sot_w1d_loss_and_grad
+ * returns for the widened rows on the same kernel family, rne = round to nearest even (sot_rows_f32_to_bf16's) -- or rne(v * *rescale) when
+ * `rescale` is given: one float32 multiply, then the single rounding.  Row losses and the mean equal the float32 call's bits.
+ *   NATIVE: sot_w1d_bf16_native(prob) -- the typed forward's native condition on the problem (shared positions, n == m in {512, 1024, 2048,
+ *     4096}, neither SOT_FLAG_PRENORMALIZED nor SOT_FLAG_NO_SPECIALIZE, x and y 16-byte aligned with row strides that are multiples of 8
+ *     elements) without SOT_FLAG_TIE_FREE_GRADIENT (the merge-free training form has no 16-bit instantiation; the flag means nothing to a
+ *     forward call) -- AND grad_x / grad_y 16-byte aligned.  The full-row backward kernels read the 16-bit rows and round each gradient at its
+ *     store: no float32 image of a spectrum or of a gradient exists, and the workspace is exactly sot_workspace_bytes() of the problem.
+ *   EVERY OTHER problem runs inside the call: x and y widened into the workspace, the float32 backward / training form into float32 gradient
+ *     images there, the images narrowed into grad_x / grad_y (scaled by *rescale first).  sot_w1d_bf16_backward_workspace_bytes() reports the
+ *     images plus the float32 call's workspace; it is REQUIRED in full (SOT_ERR_NULL_POINTER without one, SOT_ERR_WORKSPACE for a shorter one,
+ *     decided before anything is enqueued); any alignment will do.  The function sees no gradient pointer: a caller whose gradient buffers are
+ *     not 16-byte aligned on an otherwise native problem asks it with SOT_FLAG_NO_SPECIALIZE added (the same sum) or gets SOT_ERR_WORKSPACE.
+ *   rescale (device scalar or NULL; non-NULL only without grad_x: SOT_ERR_BAD_SHAPE otherwise) is the FIX-UP mode of a training step that
+ *     stored its gradient before the upstream gradient was known: the call recomputes grad_y as rne(v * *rescale).  On the native route every
+ *     workgroup reads the scalar first and returns at once when it is exactly 1 -- grad_y is not touched, as with sot_scale_inplace; the
+ *     widening route rewrites grad_y with rne(v), the values it held.
+ * Refusals and B == 0 are those of sot_w1d_backward / sot_w1d_loss_and_grad.  sot_w1d_bf16_backward_workspace_bytes and sot_w1d_bf16_native:
+ * host-side arithmetic, 0 for prob == NULL, n < 1 or m < 1.  (The three other calls are declared `extern` for the reason given above; their
+ * guard-band cases, refusals and empty batches are in tests/test_bf16_train_gpu.py, and the binding lists them in _native.BF16_TRAIN_EXPORTS.) */
+size_t sot_w1d_bf16_backward_workspace_bytes(const sot_problem *prob, int want_grad_x, int want_grad_y);
+extern int sot_w1d_bf16_native(const sot_problem *prob);
+extern int sot_w1d_backward_bf16(const sot_problem *prob, const float *grad_row, int64_t grad_row_stride, float grad_scale,
+                                 uint16_t *grad_x /* [B,n] or NULL */, uint16_t *grad_y /* [B,m] or NULL */, const float *rescale /* or NULL */,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+extern int sot_w1d_loss_and_grad_bf16(const sot_problem *prob, float *row_loss /* [B] */, double denom, float *mean_out, double *sum_out,
+                                      float grad_scale, uint16_t *grad_y /* [B,m] */, uint32_t *completion_counters /* or NULL */,
+                                      void *workspace, size_t workspace_bytes, void *stream);
 
 /* out[c] = sum_r rows[r * row_stride + c], c < n, in a fixed order with fp64 accumulation (B == 0: zeros). */
 int sot_column_sum(const float *rows, int64_t B, int32_t n, int64_t row_stride, float *out /* [n] */, void *stream);
