@@ -457,21 +457,87 @@ def workspace(pr: SotProblem, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
+# ---- the four calls on weight rows, each ONE marshalling helper for both element types.  What a pair differs by is passed in: the C function,
+# the dtype of the gradient rows, and the workspace query ws(pr, dev, flags, plan, need_gx, need_gy).
+
+def _grad_row_arg(grad_row, B):
+    """(contiguous tensor, element stride 0 / 1) of an upstream row gradient: [B], or one element that is broadcast to every row."""
+    g = grad_row.contiguous()
+    stride = 0 if g.numel() == 1 else 1
+    if stride == 1 and g.numel() != B:
+        raise RuntimeError(f"grad_row has {g.numel()} elements for {B} rows")
+    return g, stride
+
+
+def _ws_f32(pr, dev, flags, plan, need_gx=False, need_gy=False):
+    """The float32 calls decide in Python whether there is a workspace at all: no FFI call for the size on the hot path."""
+    return workspace(pr, dev) if _needs_workspace(pr, flags, plan) else None
+
+
+def _forward_rows(fn, ws_of, x, y, xpos, ypos, p, flags, plan, out=None, perm_out=None, perm_in=None):
+    dev = x.device
+    row_loss = out if out is not None else torch.empty(x.shape[0], dtype=torch.float32, device=dev)
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_out, perm_in)
+    ws = ws_of(pr, dev, flags, plan)
+    with _on_device(dev):
+        rc = fn(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return row_loss
+
+
+def _loss_fused(fn, ws_of, x, y, xpos, ypos, p, flags, plan, denom, hinge, want_sum=False, fused_mean=False, row_out=None, mean_out=None,
+                sum_out=None):
+    dev = x.device
+    B = x.shape[0]
+    row_loss = row_out if row_out is not None else torch.empty(B, dtype=torch.float32, device=dev)
+    mean = mean_out if mean_out is not None else torch.empty((), dtype=torch.float32, device=dev)
+    total = sum_out if sum_out is not None else (torch.empty((), dtype=torch.float64, device=dev) if want_sum else None)
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = ws_of(pr, dev, flags, plan)
+    with _on_device(dev):
+        rc = fn(ctypes.byref(pr), row_loss.data_ptr(), float(B if denom is None else denom), 0 if hinge is None else 1,
+                0.0 if hinge is None else float(hinge), mean.data_ptr(), _ptr(total), completion_counters(dev) if _want_tail(fused_mean) else None,
+                _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return mean, row_loss, total
+
+
+def _loss_and_grad(fn, grad_dtype, ws_of, x, y, xpos, ypos, p, flags, plan, fused_mean):
+    dev = x.device
+    B, m = x.shape[0], y.shape[1]
+    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    gy = torch.empty(B, m, dtype=grad_dtype, device=dev)
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
+    ws = ws_of(pr, dev, flags, plan, False, True)
+    with _on_device(dev):
+        rc = fn(ctypes.byref(pr), row_loss.data_ptr(), float(B), mean.data_ptr(), None, 1.0 / B, gy.data_ptr(),
+                completion_counters(dev) if _want_tail(fused_mean) else None, _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return mean, row_loss, gy
+
+
+def _backward_rows(fn, grad_dtype, ws_of, x, y, xpos, ypos, p, flags, grad_row, need_gx, need_gy, plan, grad_scale, perm_in=None, gy_out=None, extra=()):
+    """grad_row: _grad_row_arg()'s pair; extra: the arguments of the C function between the gradient pointers and the workspace (the typed call's rescale)."""
+    dev = x.device
+    B, n = x.shape
+    m = y.shape[1]
+    gx = torch.empty(B, n, dtype=grad_dtype, device=dev) if need_gx else None
+    gy = (gy_out if gy_out is not None else torch.empty(B, m, dtype=grad_dtype, device=dev)) if need_gy else None
+    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_in=perm_in)
+    ws = ws_of(pr, dev, flags, plan, need_gx, need_gy)
+    g, stride = grad_row
+    with _on_device(dev):
+        rc = fn(ctypes.byref(pr), _ptr(g), stride, float(grad_scale), _ptr(gx), _ptr(gy), *extra, _ptr(ws), ws.numel() if ws is not None else 0,
+                stream_ptr(dev))
+    check(rc, p)
+    return gx, gy
+
+
 def forward_rows(x, y, xpos, ypos, p, flags, plan=None, out=None, perm_out=None, perm_in=None) -> torch.Tensor:
     """row_loss[B] = W_p^p per row (sot_w1d_forward).  perm_out / perm_in: row_permutations() buffers (per-row positions: the sort's
     permutations are left there / taken from there)."""
-    lib = load()
-    dev = x.device
-    B = x.shape[0]
-    row_loss = out if out is not None else torch.empty(B, dtype=torch.float32, device=dev)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_out, perm_in)
-    need_ws = _needs_workspace(pr, flags, plan)
-    ws = workspace(pr, dev) if need_ws else None
-    with _on_device(dev):
-        rc = lib.sot_w1d_forward(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0,
-                                 stream_ptr(dev))
-    check(rc, p)
-    return row_loss
+    return _forward_rows(load().sot_w1d_forward, _ws_f32, x, y, xpos, ypos, p, flags, plan, out, perm_out, perm_in)
 
 
 def loss_fused(x, y, xpos, ypos, p, flags, plan=None, denom=None, hinge=None, want_sum=False, fused_mean=None, row_out=None,
@@ -479,22 +545,19 @@ def loss_fused(x, y, xpos, ypos, p, flags, plan=None, denom=None, hinge=None, wa
     """Forward + batch mean behind one FFI call (sot_w1d_loss): the forward kernel and the mean kernel back to back, or --
     fused_mean=True (default: module switch FUSED_MEAN) -- ONE kernel whose last workgroup reduces the row losses (same bits).  Returns (mean 0-d fp32, row_loss [B], sum fp64 or None).
     row_out / mean_out / sum_out: optional preallocated outputs ([B] fp32, 1-element fp32, 1-element fp64)."""
-    lib = load()
-    dev = x.device
-    B = x.shape[0]
-    row_loss = row_out if row_out is not None else torch.empty(B, dtype=torch.float32, device=dev)
-    mean = mean_out if mean_out is not None else torch.empty((), dtype=torch.float32, device=dev)
-    total = sum_out if sum_out is not None else (torch.empty((), dtype=torch.float64, device=dev) if want_sum else None)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
-    need_ws = _needs_workspace(pr, flags, plan)
-    ws = workspace(pr, dev) if need_ws else None
-    with _on_device(dev):
-        rc = lib.sot_w1d_loss(ctypes.byref(pr), row_loss.data_ptr(), float(B if denom is None else denom),
-                              0 if hinge is None else 1, 0.0 if hinge is None else float(hinge), mean.data_ptr(),
-                              _ptr(total), completion_counters(dev) if _want_tail(fused_mean) else None,
-                              _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return mean, row_loss, total
+    return _loss_fused(load().sot_w1d_loss, _ws_f32, x, y, xpos, ypos, p, flags, plan, denom, hinge, want_sum, fused_mean, row_out, mean_out, sum_out)
+
+
+def loss_and_grad(x, y, xpos, ypos, p, flags, plan=None, fused_mean=None):
+    """Training form (sot_w1d_loss_and_grad): (mean 0-d fp32, row_loss [B], d mean / d y [B, m]) -- one pass over the rows
+    where a compile-time backward kernel exists."""
+    return _loss_and_grad(load().sot_w1d_loss_and_grad, torch.float32, _ws_f32, x, y, xpos, ypos, p, flags, plan, fused_mean)
+
+
+def backward_rows(x, y, xpos, ypos, p, flags, grad_row, need_gx=True, need_gy=True, plan=None, grad_scale=1.0, perm_in=None):
+    """grad_row: [B] tensor, or a 0-d / 1-element tensor that is broadcast to every row (stride 0).  perm_in: the forward's row_permutations()."""
+    return _backward_rows(load().sot_w1d_backward, torch.float32, _ws_f32, x, y, xpos, ypos, p, flags, _grad_row_arg(grad_row, x.shape[0]), need_gx, need_gy,
+                          plan, grad_scale, perm_in)
 
 
 # ---- bfloat16 weight rows (include/sot_hip.h, ABI 19): row conversion and the typed forward.  Results are those of the float32 calls on
@@ -530,7 +593,7 @@ def _require_bf16_rows(x, y, xpos, ypos):
             raise TypeError(f"the typed forward takes bfloat16 GPU weights for both measures; got {t.dtype} on {t.device}")
 
 
-def bf16_workspace(pr: SotProblem, device):
+def bf16_workspace(pr: SotProblem, device, flags=None, plan=None):
     """The workspace of a typed call: exactly sot_w1d_bf16_workspace_bytes() -- the float32 call's own for a native problem, plus the two
     widened copies for every other one -- or None when the call needs none."""
     nbytes = int(load().sot_w1d_bf16_workspace_bytes(ctypes.byref(pr)))
@@ -541,32 +604,14 @@ def forward_rows_bf16(x, y, xpos, ypos, p, flags, plan=None) -> torch.Tensor:
     """row_loss[B] (float32) for bfloat16 weights x, y and float32 positions (sot_w1d_forward_bf16)."""
     lib = load()
     _require_bf16_rows(x, y, xpos, ypos)
-    dev = x.device
-    row_loss = torch.empty(x.shape[0], dtype=torch.float32, device=dev)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
-    ws = bf16_workspace(pr, dev)
-    with _on_device(dev):
-        rc = lib.sot_w1d_forward_bf16(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return row_loss
+    return _forward_rows(lib.sot_w1d_forward_bf16, bf16_workspace, x, y, xpos, ypos, p, flags, plan)
 
 
 def loss_fused_bf16(x, y, xpos, ypos, p, flags, plan=None, denom=None, hinge=None):
     """Forward + batch mean for bfloat16 weights behind one call (sot_w1d_loss_bf16): (mean 0-d float32, row_loss [B] float32)."""
     lib = load()
     _require_bf16_rows(x, y, xpos, ypos)
-    dev = x.device
-    B = x.shape[0]
-    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
-    mean = torch.empty((), dtype=torch.float32, device=dev)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
-    ws = bf16_workspace(pr, dev)
-    with _on_device(dev):
-        rc = lib.sot_w1d_loss_bf16(ctypes.byref(pr), row_loss.data_ptr(), float(B if denom is None else denom), 0 if hinge is None else 1,
-                                   0.0 if hinge is None else float(hinge), mean.data_ptr(), None, None, _ptr(ws),
-                                   ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return mean, row_loss
+    return _loss_fused(lib.sot_w1d_loss_bf16, bf16_workspace, x, y, xpos, ypos, p, flags, plan, denom, hinge)[:2]
 
 
 # ---- bfloat16 training (ABI 20): 16-bit gradients out of the backward kernels.  Each gradient element is the float32 call's element on
@@ -587,7 +632,7 @@ def bf16_native(x, y, xpos, ypos, p, flags, plan=None) -> bool:
     return bool(load().sot_w1d_bf16_native(ctypes.byref(pr)))
 
 
-def _bf16_backward_workspace(pr: SotProblem, device, need_gx, need_gy):
+def _bf16_backward_workspace(pr: SotProblem, device, flags, plan, need_gx, need_gy):
     nbytes = int(load().sot_w1d_bf16_backward_workspace_bytes(ctypes.byref(pr), int(need_gx), int(need_gy)))
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes > 0 else None
 
@@ -598,45 +643,20 @@ def backward_rows_bf16(x, y, xpos, ypos, p, flags, grad_row, need_gx=True, need_
     rne(gradient * rescale), or left as it is when rescale is exactly 1."""
     lib = load()
     _require_bf16_rows(x, y, xpos, ypos)
-    dev = x.device
-    B, n = x.shape
-    m = y.shape[1]
-    gx = torch.empty(B, n, dtype=torch.bfloat16, device=dev) if need_gx else None
-    gy = (gy_out if gy_out is not None else torch.empty(B, m, dtype=torch.bfloat16, device=dev)) if need_gy else None
-    if gy_out is not None and (gy_out.dtype != torch.bfloat16 or tuple(gy_out.shape) != (B, m) or not gy_out.is_contiguous()):
+    if gy_out is not None and (gy_out.dtype != torch.bfloat16 or tuple(gy_out.shape) != (x.shape[0], y.shape[1]) or not gy_out.is_contiguous()):
         raise RuntimeError("gy_out must be a contiguous bfloat16 [B, m] tensor")
     if rescale is not None and (need_gx or rescale.dtype != torch.float32 or rescale.numel() != 1 or not rescale.is_cuda):
         raise RuntimeError("rescale is a one-element float32 device tensor of a y-only call")
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
-    ws = _bf16_backward_workspace(pr, dev, need_gx, need_gy)
-    g = grad_row.contiguous() if grad_row is not None else None
-    stride = 0 if (g is None or g.numel() == 1) else 1
-    if stride == 1 and g.numel() != B:
-        raise RuntimeError(f"grad_row has {g.numel()} elements for {B} rows")
-    with _on_device(dev):
-        rc = lib.sot_w1d_backward_bf16(ctypes.byref(pr), _ptr(g), stride, float(grad_scale), _ptr(gx), _ptr(gy), _ptr(rescale), _ptr(ws),
-                                       ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return gx, gy
+    g = (None, 0) if grad_row is None else _grad_row_arg(grad_row, x.shape[0])   # None: 1 for every row
+    return _backward_rows(lib.sot_w1d_backward_bf16, torch.bfloat16, _bf16_backward_workspace, x, y, xpos, ypos, p, flags, g, need_gx, need_gy,
+                          plan, grad_scale, gy_out=gy_out, extra=(_ptr(rescale),))
 
 
 def loss_and_grad_bf16(x, y, xpos, ypos, p, flags, plan=None, fused_mean=None):
     """Training form for bfloat16 weights (sot_w1d_loss_and_grad_bf16): (mean 0-d float32, row_loss [B] float32, d mean / d y [B, m] bfloat16)."""
     lib = load()
     _require_bf16_rows(x, y, xpos, ypos)
-    dev = x.device
-    B, m = x.shape[0], y.shape[1]
-    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
-    mean = torch.empty((), dtype=torch.float32, device=dev)
-    gy = torch.empty(B, m, dtype=torch.bfloat16, device=dev)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
-    ws = _bf16_backward_workspace(pr, dev, False, True)
-    with _on_device(dev):
-        rc = lib.sot_w1d_loss_and_grad_bf16(ctypes.byref(pr), row_loss.data_ptr(), float(B), mean.data_ptr(), None, 1.0 / B, gy.data_ptr(),
-                                            completion_counters(dev) if _want_tail(fused_mean) else None,
-                                            _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return mean, row_loss, gy
+    return _loss_and_grad(lib.sot_w1d_loss_and_grad_bf16, torch.bfloat16, _bf16_backward_workspace, x, y, xpos, ypos, p, flags, plan, fused_mean)
 
 
 def prepared_loss_call(x, y, xpos, ypos, p, flags, plan, row_out, mean_out, sum_out=None, stream=None):
@@ -663,26 +683,6 @@ def prepared_loss_call(x, y, xpos, ypos, p, flags, plan, row_out, mean_out, sum_
             check(rc, p)
         return keep[6]
     return call
-
-
-def loss_and_grad(x, y, xpos, ypos, p, flags, plan=None, fused_mean=None):
-    """Training form (sot_w1d_loss_and_grad): (mean 0-d fp32, row_loss [B], d mean / d y [B, m]) -- one pass over the rows
-    where a compile-time backward kernel exists."""
-    lib = load()
-    dev = x.device
-    B, m = x.shape[0], y.shape[1]
-    row_loss = torch.empty(B, dtype=torch.float32, device=dev)
-    mean = torch.empty((), dtype=torch.float32, device=dev)
-    gy = torch.empty(B, m, dtype=torch.float32, device=dev)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan)
-    need_ws = _needs_workspace(pr, flags, plan)
-    ws = workspace(pr, dev) if need_ws else None
-    with _on_device(dev):
-        rc = lib.sot_w1d_loss_and_grad(ctypes.byref(pr), row_loss.data_ptr(), float(B), mean.data_ptr(), None, 1.0 / B, gy.data_ptr(),
-                                       completion_counters(dev) if _want_tail(fused_mean) else None,
-                                       _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return mean, row_loss, gy
 
 
 def profile_next_launch(slot: int):
@@ -722,28 +722,6 @@ def reduce_mean(row_loss, denom=None, hinge=None, want_sum=False, sum_out=None):
     return (mean, total) if want_sum else mean
 
 
-def backward_rows(x, y, xpos, ypos, p, flags, grad_row, need_gx=True, need_gy=True, plan=None, grad_scale=1.0, perm_in=None):
-    """grad_row: [B] tensor, or a 0-d / 1-element tensor that is broadcast to every row (stride 0).  perm_in: the forward's row_permutations()."""
-    lib = load()
-    dev = x.device
-    B, n = x.shape
-    m = y.shape[1]
-    gx = torch.empty(B, n, dtype=torch.float32, device=dev) if need_gx else None
-    gy = torch.empty(B, m, dtype=torch.float32, device=dev) if need_gy else None
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_in=perm_in)
-    need_ws = _needs_workspace(pr, flags, plan)
-    ws = workspace(pr, dev) if need_ws else None
-    g = grad_row.contiguous()
-    stride = 0 if g.numel() == 1 else 1
-    if stride == 1 and g.numel() != B:
-        raise RuntimeError(f"grad_row has {g.numel()} elements for {B} rows")
-    with _on_device(dev):
-        rc = lib.sot_w1d_backward(ctypes.byref(pr), g.data_ptr(), stride, float(grad_scale), _ptr(gx), _ptr(gy), _ptr(ws),
-                                  ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return gx, gy
-
-
 def position_grads(x, y, xpos, ypos, p, flags, grad_row, need_x=True, need_y=True, plan=None, grad_scale=1.0, perm_in=None):
     """Gradients w.r.t. the support positions (sot_w1d_position_grad): per-row [B, n] / [B, m] for per-row positions; for a shared
     position row the batch sum [n] / [m] (sot_column_sum), which is what autograd's expand backward returns (losses.py:167-170)."""
@@ -754,12 +732,8 @@ def position_grads(x, y, xpos, ypos, p, flags, grad_row, need_x=True, need_y=Tru
     gxp = torch.empty(B, n, dtype=torch.float32, device=dev) if need_x else None
     gyp = torch.empty(B, m, dtype=torch.float32, device=dev) if need_y else None
     pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_in=perm_in)
-    need_ws = _needs_workspace(pr, flags, plan)
-    ws = workspace(pr, dev) if need_ws else None
-    g = grad_row.contiguous()
-    stride = 0 if g.numel() == 1 else 1
-    if stride == 1 and g.numel() != B:
-        raise RuntimeError(f"grad_row has {g.numel()} elements for {B} rows")
+    ws = _ws_f32(pr, dev, flags, plan)
+    g, stride = _grad_row_arg(grad_row, B)
     out = []
     with _on_device(dev):
         rc = lib.sot_w1d_position_grad(ctypes.byref(pr), g.data_ptr(), stride, float(grad_scale), _ptr(gxp), _ptr(gyp), _ptr(ws),
@@ -811,14 +785,6 @@ def mixed_problem(x, y, xpos, ypos, p, flags, plan=None) -> SotProblem:
 def _mixed_workspace(lib, pr, device):
     nbytes = int(lib.sot_w1d_mixed_workspace_bytes(ctypes.byref(pr)))
     return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
-
-
-def _grad_row_arg(grad_row, B):
-    g = grad_row.contiguous()
-    stride = 0 if g.numel() == 1 else 1
-    if stride == 1 and g.numel() != B:
-        raise RuntimeError(f"grad_row has {g.numel()} elements for {B} rows")
-    return g, stride
 
 
 def mixed_forward_rows(x, y, xpos, ypos, p, flags, plan=None) -> torch.Tensor:

@@ -1,8 +1,10 @@
-// sot_bf16.hip -- bfloat16 weight rows (ABI 19): the two row-conversion kernels (bf16 -> f32, f32 -> bf16 with round to nearest even), the
-// instantiations of the full-row forward kernels that read 16-bit rows directly (sot_full_fwd.hpp: sot_area_full_kernel and
-// sot_forward_full_kernel with WT = uint16_t) and the typed entry points sot_w1d_forward_bf16 / sot_w1d_loss_bf16 with their workspace arithmetic.
+// sot_bf16.hip -- bfloat16 weight rows (ABI 19 / 20): the two row-conversion kernels (bf16 -> f32, f32 -> bf16 with round to nearest even) and
+// their entry points, the instantiations of the full-row forward kernels that read 16-bit rows directly (sot_full_fwd.hpp: the shared geometry
+// tables with WT = uint16_t), the native routes' condition, and the typed call (bf16_rows_call) through which all four typed entry points
+// run the bodies of their float32 twins (sot_hip.hip); sot_w1d_forward_bf16 / sot_w1d_loss_bf16 are here, the two of the backward in
+// sot_bf16_bwd.hip.  Routing is not: run_forward / run_backward (sot_hip.hip) route both element types.
 // A bfloat16 is the upper half of a float32, so widening is exact and "upcast, then the float32 arithmetic" defines every result: the
-// native kernels widen in the register behind the load, every other problem is widened into the workspace and takes run_forward as it is.
+// native kernels widen in the register behind the load, every other problem is widened into the workspace and takes the float32 call as it is.
 #include "sot_full_fwd.hpp"
 
 namespace sot {
@@ -108,83 +110,72 @@ int launch_rows_f32_to_bf16(const float* src, int64_t B, int n, int64_t ss, uint
 }
 
 // ---------------------------------------------------------------------------------------------
-// Native 16-bit rows: the geometries that a row fills, on shared positions (the NX == 0 set without 8192 bins)
+// Native 16-bit rows: the merge-free and the merge kernels of the shared geometry tables (sot_full_fwd.hpp) are compiled into this object
 // ---------------------------------------------------------------------------------------------
-static hipError_t dispatch_area_full_bf16(const FwdArgs& a, hipStream_t s)
-{
-    switch (a.n) {
-        case 512: return dispatch_area_full_bf16_g<64, 8, 4>(a, s);
-        case 1024: return dispatch_area_full_bf16_g<128, 8, 2>(a, s);
-        case 2048: return dispatch_area_full_bf16_g<256, 8, 1>(a, s);
-        case 4096: return dispatch_area_full_bf16_g<512, 8, 1>(a, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
+template hipError_t dispatch_area_full_pow2<uint16_t>(const FwdArgs& a, hipStream_t s);
+template hipError_t dispatch_forward_full_pow2<uint16_t>(int pm, const FwdArgs& a, hipStream_t s);
 
-static hipError_t dispatch_forward_full_bf16(int pm, const FwdArgs& a, hipStream_t s)
-{
-    switch (a.n) {
-        case 512: return dispatch_forward_full_bf16_g<64, 8, 4>(pm, a, s);
-        case 1024: return dispatch_forward_full_bf16_g<128, 8, 2>(pm, a, s);
-        case 2048: return dispatch_forward_full_bf16_g<256, 8, 1>(pm, a, s);
-        case 4096: return dispatch_forward_full_bf16_g<512, 8, 1>(pm, a, s);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
-// The native route's condition (host side; sot_w1d_bf16_workspace_bytes reports by the same predicate): shared positions, n == m in the
-// set above, kernels with the length at compile time allowed, weights normalised by the call, rows of x and y on 16-byte boundaries
-// (pointer 16-byte aligned, row strides multiples of 8 elements).
-bool bf16_native(const sot_problem* pr)
+// The native routes' condition on the PROBLEM (host side; sot_w1d_bf16_native and the two workspace functions report by it): shared positions,
+// n == m in the set of the tables above, kernels with the length at compile time allowed, weights normalised by the call, rows of x and y on
+// 16-byte boundaries (pointer 16-byte aligned, row strides multiples of 8 elements).  backward: not the opt-in merge-free training form either,
+// which has no 16-bit instantiation (the forward ignores that flag, as the float32 forward does).  A call adds the condition on its buffers:
+// gradient rows on 16-byte boundaries (bf16_rows_call).
+bool bf16_native(const sot_problem* pr, bool backward)
 {
     return pr->xpos_row_stride == 0 && pr->ypos_row_stride == 0 && pr->n == pr->m &&
            (pr->n == 512 || pr->n == 1024 || pr->n == 2048 || pr->n == 4096) &&
-           !(pr->flags & (SOT_FLAG_PRENORMALIZED | SOT_FLAG_NO_SPECIALIZE)) &&
+           !(pr->flags & (SOT_FLAG_PRENORMALIZED | SOT_FLAG_NO_SPECIALIZE)) && !(backward && (pr->flags & SOT_FLAG_TIE_FREE_GRADIENT)) &&
            ((reinterpret_cast<uintptr_t>(pr->x) | reinterpret_cast<uintptr_t>(pr->y)) & 15) == 0 && (pr->x_row_stride & 7) == 0 && (pr->y_row_stride & 7) == 0;
 }
 
-// widened copies at the front of the workspace: [x as float32, dense | y as float32, dense | the float32 call's own workspace]
-struct WidenLayout { size_t xf, yf, inner, total; };
-static inline WidenLayout widen_layout(const sot_problem* pr)
+// the float32 images of a widened call at the front of the workspace:
+// [x, dense | y, dense | grad_x, dense (if asked for) | grad_y, dense (if asked for) | the float32 call's own workspace]
+struct WidenLayout { size_t xf, yf, gxf, gyf, inner, total; };
+static inline WidenLayout widen_layout(const sot_problem* pr, bool want_x, bool want_y)
 {
     WidenLayout w;
     const size_t B = pr->B > 0 ? (size_t)pr->B : 0;
-    w.xf = 16;   // room to move the first copy up to a 16-byte boundary, whatever the workspace's own alignment
-    w.yf = w.xf + align_up(B * (size_t)pr->n * sizeof(float), 256);
-    w.inner = w.yf + align_up(B * (size_t)pr->m * sizeof(float), 256);
+    const size_t xb = align_up(B * (size_t)pr->n * sizeof(float), 256), yb = align_up(B * (size_t)pr->m * sizeof(float), 256);
+    w.xf = 16;   // room to move the first image up to a 16-byte boundary, whatever the workspace's own alignment
+    w.yf = w.xf + xb;
+    w.gxf = w.yf + yb;
+    w.gyf = w.gxf + (want_x ? xb : 0);
+    w.inner = w.gyf + (want_y ? yb : 0);
     w.total = w.inner + sot_workspace_bytes(pr);
     return w;
 }
 
-static int run_forward_bf16(const sot_problem* pr, float* row_loss, void* workspace, size_t workspace_bytes, void* stream, const MeanTail* mean_tail)
+size_t bf16_workspace_bytes(const sot_problem* pr, bool backward, bool want_x, bool want_y)
+{
+    if (pr == nullptr || pr->n < 1 || pr->m < 1) return 0;
+    return bf16_native(pr, backward) ? sot_workspace_bytes(pr) : widen_layout(pr, want_x, want_y).total;
+}
+
+// A call on bfloat16 rows x, y (backward: with bfloat16 gradient rows gx, gy).  Native problems: `call` on the rows as they are.  Every other
+// problem: widen, the float32 call as it is, narrow -- one rounding to nearest even of the float32 gradient, the fix-up multiply in front of it.
+// Every refusal is decided before anything is enqueued.
+int bf16_rows_call(const sot_problem* pr, bool backward, uint16_t* gx, uint16_t* gy, const float* rescale, void* workspace, size_t workspace_bytes,
+                   void* stream, const RowsCall& call)
 {
     int rc = validate(pr);
     if (rc != SOT_OK) return rc;
-    if (bf16_native(pr)) {
-        Launch l;
-        rc = setup_launch(pr, false, workspace, workspace_bytes, stream, &l);   // positions, plan, flags: nothing in it follows x or y
-        if (rc != SOT_OK) return rc;
-        if (pr->B == 0) return SOT_OK;
-        l.a.row_loss = row_loss;
-        if (mean_tail != nullptr && row_loss != nullptr) l.a.mt = *mean_tail;
-        // the route family of run_forward for these rows: merge-free for p = 1 on one grid without cutoff, the merge walk otherwise
-        const bool area = l.pm == 1 && (pr->flags & SOT_FLAG_SAME_GRID) && !(pr->flags & (SOT_FLAG_LIMIT_Q | SOT_FLAG_NO_AREA));
-        return launch_status(area ? dispatch_area_full_bf16(l.a, l.s) : dispatch_forward_full_bf16(l.pm, l.a, l.s));
-    }
-    // every other problem: widen, then the float32 call as it is.  Refusals are decided before the conversions are enqueued.
+    if (rescale != nullptr && gx != nullptr) return SOT_ERR_BAD_SHAPE;   // the fix-up mode belongs to the y-only call
+    if (bf16_native(pr, backward) && ((reinterpret_cast<uintptr_t>(gx) | reinterpret_cast<uintptr_t>(gy)) & 15) == 0)
+        return call(Elem::bf16, pr, reinterpret_cast<float*>(gx), reinterpret_cast<float*>(gy), rescale, workspace, workspace_bytes);
     {
         LaunchCfg cfg; size_t lds; int block, rpw;
-        if (!pick_cfg(pr->n, pr->m, pr->xpos_row_stride != 0, false, &cfg, &lds, &block, &rpw)) return SOT_ERR_UNSUPPORTED_SIZE;
+        if (!pick_cfg(pr->n, pr->m, pr->xpos_row_stride != 0, backward, &cfg, &lds, &block, &rpw)) return SOT_ERR_UNSUPPORTED_SIZE;
     }
-    if (pr->B == 0) return run_forward(pr, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, stream, mean_tail);
-    const WidenLayout w = widen_layout(pr);
+    if (pr->B == 0 || (backward && gx == nullptr && gy == nullptr))   // nothing follows x or y: the float32 call's own answer
+        return call(Elem::f32, pr, nullptr, nullptr, nullptr, workspace, workspace_bytes);
+    const WidenLayout w = widen_layout(pr, gx != nullptr, gy != nullptr);
     if (workspace == nullptr) return SOT_ERR_NULL_POINTER;
     if (workspace_bytes < w.total) return SOT_ERR_WORKSPACE;
     char* const base = reinterpret_cast<char*>(workspace);
     const size_t lead = (size_t)((16 - (reinterpret_cast<uintptr_t>(base) & 15)) & 15);   // <= 15 < w.xf
-    float* const xf = reinterpret_cast<float*>(base + lead);
-    float* const yf = reinterpret_cast<float*>(base + lead + (w.yf - w.xf));
-    char* const inner = base + lead + (w.inner - w.xf);
+    const auto image = [&](size_t off) { return reinterpret_cast<float*>(base + lead + (off - w.xf)); };
+    float* const xf = image(w.xf); float* const yf = image(w.yf);
+    float* const gxf = gx != nullptr ? image(w.gxf) : nullptr; float* const gyf = gy != nullptr ? image(w.gyf) : nullptr;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     rc = launch_rows_bf16_to_f32(reinterpret_cast<const uint16_t*>(pr->x), pr->B, pr->n, pr->x_row_stride, xf, pr->n, s);
     if (rc != SOT_OK) return rc;
@@ -192,7 +183,12 @@ static int run_forward_bf16(const sot_problem* pr, float* row_loss, void* worksp
     if (rc != SOT_OK) return rc;
     sot_problem wide = *pr;
     wide.x = xf; wide.y = yf; wide.x_row_stride = pr->n; wide.y_row_stride = pr->m;
-    return run_forward(&wide, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, inner, w.total - w.inner, stream, mean_tail);
+    rc = call(Elem::f32, &wide, gxf, gyf, nullptr, image(w.inner), w.total - w.inner);
+    if (rc == SOT_OK && gxf != nullptr) rc = launch_rows_f32_to_bf16(gxf, pr->B, pr->n, pr->n, gx, pr->n, s);
+    if (rc == SOT_OK && gyf != nullptr && rescale != nullptr)   // float32 multiply in front of the one rounding (a no-op kernel when the scalar is exactly 1)
+        rc = sot_scale_inplace(gyf, pr->B * (int64_t)pr->m, rescale, stream);
+    if (rc == SOT_OK && gyf != nullptr) rc = launch_rows_f32_to_bf16(gyf, pr->B, pr->m, pr->m, gy, pr->m, s);
+    return rc;
 }
 
 }  // namespace sot
@@ -213,29 +209,18 @@ int sot_rows_f32_to_bf16(const float* src, int64_t B, int32_t n, int64_t src_row
     return sot::launch_rows_f32_to_bf16(src, B, (int)n, src_row_stride, dst, dst_row_stride, reinterpret_cast<hipStream_t>(stream));
 }
 
-size_t sot_w1d_bf16_workspace_bytes(const sot_problem* prob)
-{
-    if (prob == nullptr || prob->n < 1 || prob->m < 1) return 0;
-    return sot::bf16_native(prob) ? sot_workspace_bytes(prob) : sot::widen_layout(prob).total;
-}
+size_t sot_w1d_bf16_workspace_bytes(const sot_problem* prob) { return sot::bf16_workspace_bytes(prob, false, false, false); }
 
 int sot_w1d_forward_bf16(const sot_problem* prob, float* row_loss, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
-    return sot::run_forward_bf16(prob, row_loss, workspace, workspace_bytes, stream, nullptr);
+    return sot::forward_call(sot::Elem::bf16, prob, row_loss, workspace, workspace_bytes, stream);
 }
 
 int sot_w1d_loss_bf16(const sot_problem* prob, float* row_loss, double denom, int apply_hinge, float hinge_threshold, float* mean_out,
                       double* sum_out, uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
-    if (mean_out == nullptr && sum_out == nullptr) return SOT_ERR_NULL_POINTER;
-    if (prob != nullptr && prob->B == 0) return SOT_ERR_BAD_SHAPE;  // the mean of zero rows is undefined
-    sot::MeanTail mt{};
-    mt.counters = completion_counters; mt.denom = denom; mt.apply_hinge = apply_hinge; mt.hinge = hinge_threshold; mt.mean_out = mean_out; mt.sum_out = sum_out;
-    const int rc = sot::run_forward_bf16(prob, row_loss, workspace, workspace_bytes, stream, completion_counters ? &mt : nullptr);
-    if (rc != SOT_OK || completion_counters != nullptr) return rc;
-    return sot_w1d_reduce_mean(row_loss, prob->B, denom, apply_hinge, hinge_threshold, mean_out, sum_out, stream);
+    return sot::loss_call(sot::Elem::bf16, prob, row_loss, denom, apply_hinge, hinge_threshold, mean_out, sum_out, completion_counters, workspace,
+                          workspace_bytes, stream);
 }
 
 }  // extern "C"

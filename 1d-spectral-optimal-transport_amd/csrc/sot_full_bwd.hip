@@ -22,20 +22,9 @@ hipError_t dispatch_area_train(const BwdArgs& b, hipStream_t s)
 }
 bool area_train_supports(int n) { return n == 512 || n == 1024 || n == 2048 || n == 4096 || n == 129 || n == 257 || n == 513 || n == 1025 || n == 2049; }
 
-// Rows per workgroup of the y-only (training) kernel for 2048-bin rows.  Without gradient slots for U two rows and the shared
-// position copy take 68.7 KB: two workgroups = four rows per CU instead of three (one row with U slots + positions: 50.9 KB).
-// Measured at 8192 x 2048, paper mode: 79.7 instead of 81.5 us.
 hipError_t dispatch_backward_full(int pm, const BwdArgs& b, hipStream_t s)
 {
     switch (b.f.n) {
-        case 512: return dispatch_backward_full_g<64, 8, 4>(pm, b, s);   // (the slim layout adds a fourth workgroup per CU here too: 64.5 vs 65.0 us, nothing)
-        case 1024:   // y-only: 34.8 instead of 43.3 KB per two rows = eight rows per CU instead of six: 16384 rows 78.8 -> 73.4 us, 4096 rows 27.3 -> 26.0 us
-            if (b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, 0, true, 1>(pm, b, s);
-            return dispatch_backward_full_g<128, 8, 2, 0, 1>(pm, b, s);
-        case 2048:
-            if (b.gx == nullptr) return dispatch_backward_full_y<256, 8, 2>(pm, b, s);
-            return dispatch_backward_full_g<256, 8, 1, 0, 1>(pm, b, s);
-        case 4096: return dispatch_backward_full_g<512, 8, 1>(pm, b, s);
         case 129: return dispatch_backward_full_g<64, 3, 4, 129>(pm, b, s);
         case 2049:   // y-only: 47.7 instead of 57 KB per row = three rows per CU instead of two: 8192 rows 119.2 -> 95.5 us
             if (b.gx == nullptr) return dispatch_backward_full_y<256, 9, 1, 2049, true, 1>(pm, b, s);
@@ -51,7 +40,7 @@ hipError_t dispatch_backward_full(int pm, const BwdArgs& b, hipStream_t s)
             // (128 VGPRs, 9 dwords spilled) holds eight rows per CU instead of six: 4096 rows 30.8 -> 29.1 us, 16384 rows 88.9 -> 85.6 us
             if (b.gx == nullptr) return dispatch_backward_full_y<128, 9, 2, 1025, true, 4>(pm, b, s);
             return dispatch_backward_full_g<128, 9, 2, 1025, 1>(pm, b, s);
-        default: return hipErrorInvalidConfiguration;
+        default: return dispatch_backward_full_pow2<float>(pm, b, s);   // 512 ... 4096 bins: the table shared with the 16-bit rows (sot_full_bwd.hpp)
     }
 }
 

@@ -1,7 +1,8 @@
 // sot_full_bwd.hpp -- backward kernels of the full-row family (compile-time geometries) with their launch and dispatch templates,
 // namespace sot: the merge backward and the merge-free p = 1 training form.  Included by the objects that instantiate them:
-// sot_full_bwd.hip (compile-time row lengths) and sot_full_rt_bwd.hip (run-time row lengths), where the non-template dispatch
-// functions live (dispatch_backward_full, dispatch_area_train, ...).  The forward side is sot_full_fwd.hpp.
+// sot_full_bwd.hip (compile-time row lengths), sot_full_rt_bwd.hip (run-time row lengths) and sot_bf16_bwd.hip (16-bit rows and gradients).
+// The non-template dispatch functions live in the first two (dispatch_backward_full, dispatch_area_train, ...); the geometry table of
+// 512 ... 4096 bins, which both element types share, is a template here (dispatch_backward_full_pow2).  The forward side is sot_full_fwd.hpp.
 #pragma once
 #include "sot_full_common.hpp"
 
@@ -647,6 +648,35 @@ static hipError_t dispatch_backward_full_y(int pm, const BwdArgs& b, hipStream_t
         using M = decltype(md);
         return launch_backward_full_x<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX, false, SLIM, MINB, false, WT, GT>(b, s);
     });
+}
+
+// Waves per SIMD the y-only kernel of 2048-bin rows is compiled for (MINB) -- the one geometry choice that follows the element type.  16-bit
+// rows: four.  Uncapped, the modes without square_dist take 129 / 130 VGPRs (float32: 125 / 126), and at three waves per SIMD only ONE of these
+// 8-wave workgroups is resident on a CU instead of the two its LDS allows.  (The both-gradient kernel's 129 VGPRs under square_dist cost
+// nothing: one row with U slots takes 50.9 KB, three 4-wave workgroups per CU either way.)
+template <class WT>
+constexpr int kBwdY2048MinB = std::is_same<WT, float>::value ? 1 : 4;
+
+// 512 / 1024 / 2048 / 4096 bins on shared positions: the geometries of the backward for either element type of weight and gradient rows
+// (declared in sot_launch.hpp).  y-only calls at 1024 and 2048 bins take the layout without U gradient slots:
+// 1024: 34.8 instead of 43.3 KB per two rows = eight rows per CU instead of six: 16384 rows 78.8 -> 73.4 us, 4096 rows 27.3 -> 26.0 us (float32)
+// 2048: two rows and the shared position copy take 68.7 KB: two workgroups = four rows per CU instead of three (one row with U slots +
+//       positions: 50.9 KB).  Measured at 8192 x 2048, paper mode, float32: 79.7 instead of 81.5 us.
+// (512: the slim layout adds a fourth workgroup per CU here too: 64.5 vs 65.0 us, nothing)
+template <class WT>
+hipError_t dispatch_backward_full_pow2(int pm, const BwdArgs& b, hipStream_t s)
+{
+    switch (b.f.n) {
+        case 512: return dispatch_backward_full_g<64, 8, 4, 0, 3, WT, WT>(pm, b, s);
+        case 1024:
+            if (b.gx == nullptr) return dispatch_backward_full_y<128, 8, 2, 0, true, 1, WT, WT>(pm, b, s);
+            return dispatch_backward_full_g<128, 8, 2, 0, 1, WT, WT>(pm, b, s);
+        case 2048:
+            if (b.gx == nullptr) return dispatch_backward_full_y<256, 8, 2, 0, true, kBwdY2048MinB<WT>, WT, WT>(pm, b, s);
+            return dispatch_backward_full_g<256, 8, 1, 0, 1, WT, WT>(pm, b, s);
+        case 4096: return dispatch_backward_full_g<512, 8, 1, 0, 3, WT, WT>(pm, b, s);
+        default: return hipErrorInvalidConfiguration;
+    }
 }
 
 // Per-row positions with handed-over permutations on the 2048-point geometry (round 6; see sot_forward_full_kernel: RP).  One row per workgroup;

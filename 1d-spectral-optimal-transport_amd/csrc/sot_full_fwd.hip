@@ -8,10 +8,6 @@ namespace sot {
 hipError_t dispatch_area_full(const FwdArgs& a, hipStream_t s)
 {
     switch (a.n) {
-        case 512: return dispatch_area_full_g<64, 8, 4>(a, s);
-        case 1024: return dispatch_area_full_g<128, 8, 2>(a, s);
-        case 2048: return dispatch_area_full_g<256, 8, 1>(a, s);
-        case 4096: return dispatch_area_full_g<512, 8, 1>(a, s);
         case 8192: return dispatch_area_full_g<1024, 8, 1>(a, s);
         case 129:   // two rows per wave: 65536 rows 25.3 -> 20.6 us, 4096 rows 7.9 -> 7.7 us
             return dispatch_area_half<5, 8, 129>(a, s);
@@ -22,7 +18,7 @@ hipError_t dispatch_area_full(const FwdArgs& a, hipStream_t s)
         case 1025:   // one wave per row (17 elements per thread, no workgroup barrier): 1024 / 4096 rows as before (7.4 / 10.7 us), 8192 rows 18.7 -> 16.9 us,
                      // 16384 rows 31.3 -> 29.2 us against <128, 9, 2> (interleaved A/B)
             return dispatch_area_full_g<64, 17, 4, 1025>(a, s);
-        default: return hipErrorInvalidConfiguration;
+        default: return dispatch_area_full_pow2<float>(a, s);   // 512 ... 4096 bins: the table shared with the 16-bit rows (sot_full_fwd.hpp)
     }
 }
 
@@ -63,10 +59,6 @@ bool forward_full_supports(int n, bool aligned16)
 hipError_t dispatch_forward_full(int pm, const FwdArgs& a, hipStream_t s)
 {
     switch (a.n) {
-        case 512: return dispatch_forward_full_g<64, 8, 4>(pm, a, s);
-        case 1024: return dispatch_forward_full_g<128, 8, 2>(pm, a, s);
-        case 2048: return dispatch_forward_full_g<256, 8, 1>(pm, a, s);
-        case 4096: return dispatch_forward_full_g<512, 8, 1>(pm, a, s);
         case 8192: return dispatch_forward_full_g<1024, 8, 1>(pm, a, s);
         case 129:   // large batches: two rows per wave (sot_forward_half_kernel).  Paper mode, interleaved A/B: 8192 rows 7.5 -> 6.9 us, 16384 rows 11.7 -> 10.4,
                     // 32768 rows 19.8 -> 16.0, 65536 rows 35.0 -> 28.0 us
@@ -87,7 +79,7 @@ hipError_t dispatch_forward_full(int pm, const FwdArgs& a, hipStream_t s)
             // geometry needs 17-element gradient arrays in registers and is slower: 85 -> 107 us at 16384 rows.)
             if (a.B >= kFwd1025OneWaveRows) return dispatch_forward_full_g<64, 17, 4, 1025>(pm, a, s);
             return dispatch_forward_full_g<128, 9, 2, 1025>(pm, a, s);  // 256 threads per row: 64.6 instead of 54.4 us at 16384 rows (round 1)
-        default: return hipErrorInvalidConfiguration;
+        default: return dispatch_forward_full_pow2<float>(pm, a, s);   // 512 ... 4096 bins: the table shared with the 16-bit rows (sot_full_fwd.hpp)
     }
 }
 

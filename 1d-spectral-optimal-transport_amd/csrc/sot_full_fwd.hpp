@@ -1,7 +1,9 @@
 // sot_full_fwd.hpp -- forward kernels of the full-row family (compile-time geometries) with their launch and dispatch templates,
 // namespace sot: the merge forward, the merge-free p = 1 forward (area) and their two-rows-per-wave forms.  Included by the objects
-// that instantiate them: sot_full_fwd.hip (compile-time row lengths) and sot_full_rt_fwd.hip (run-time row lengths), where the
-// non-template dispatch functions live (dispatch_forward_full, dispatch_area_full, ...).  The backward side is sot_full_bwd.hpp.
+// that instantiate them: sot_full_fwd.hip (compile-time row lengths), sot_full_rt_fwd.hip (run-time row lengths) and sot_bf16.hip (16-bit
+// rows).  The non-template dispatch functions live in the first two (dispatch_forward_full, dispatch_area_full, ...); the geometry tables
+// of 512 ... 4096 bins, which the float32 and the 16-bit rows share, are templates over the element type here (dispatch_*_full_pow2).
+// The backward side is sot_full_bwd.hpp.
 //
 // Full-row forward kernel: the row pipeline of sot_forward_kernel for row lengths known at compile time: rows that fill
 // their geometry exactly (n == m == G*CPT = 512, 2048 or 8192; 16-B aligned rows) and the paper's 257 / 513 / 1025 bins
@@ -633,40 +635,32 @@ __global__ __launch_bounds__(ROWS * 32) void sot_forward_half_kernel(const FwdAr
     if (a.mt.counters != nullptr) batch_mean_tail<ROWS * 32>(a.mt, a.row_loss, a.B, reinterpret_cast<double*>(smem));
 }
 
-template <int G, int CPT, int ROWS, bool SQ, int NX>
+// WT (here and below): the element type of the weight rows in memory -- same LDS layout, block and row groups whatever it is
+template <int G, int CPT, int ROWS, bool SQ, int NX, class WT = float>
 static hipError_t launch_area_full(const FwdArgs& a, hipStream_t s)
 {
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
-    return launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, SQ, NX>>(a, sizeof(float) * (size_t)ROWS * (size_t)L.rowf, (a.B + ROWS - 1) / ROWS,
-                                                                               ROWS * G, s);
+    return launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, SQ, NX, WT>>(a, sizeof(float) * (size_t)ROWS * (size_t)L.rowf, (a.B + ROWS - 1) / ROWS,
+                                                                                   ROWS * G, s);
 }
 
-// the bfloat16 instantiations (WT = uint16_t): same LDS layout, block and row groups as the float32 launch of the geometry
-template <int G, int CPT, int ROWS>
-static hipError_t dispatch_area_full_bf16_g(const FwdArgs& a, hipStream_t s)
-{
-    constexpr FullLayout L = full_layout<G, CPT, ROWS, false, 0>();
-    constexpr size_t lds = sizeof(float) * (size_t)ROWS * (size_t)L.rowf;
-    return (a.flags & SOT_FLAG_SQUARE) ? launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, true, 0, uint16_t>>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * G, s)
-                                       : launch_persistent_profiled<sot_area_full_kernel<G, CPT, ROWS, false, 0, uint16_t>>(a, lds, (a.B + ROWS - 1) / ROWS, ROWS * G, s);
-}
-
-template <int G, int CPT, int ROWS>
-static hipError_t dispatch_forward_full_bf16_g(int pm, const FwdArgs& a, hipStream_t s)
-{
-    constexpr FullLayout L = full_layout<G, CPT, ROWS, false, 0>();
-    static_assert(sizeof(float) * (size_t)L.total <= kLdsLimit, "workgroup fits one CU's LDS");
-    return with_mode(pm, a.flags, [&](auto md) {
-        using M = decltype(md);
-        return launch_persistent_profiled<sot_forward_full_kernel<G, CPT, ROWS, M::PM, M::LIM, M::SQ, 0, false, uint16_t>>(a, sizeof(float) * (size_t)L.total,
-                                                                                                          (a.B + ROWS - 1) / ROWS, ROWS * G, s);
-    });
-}
-
-template <int G, int CPT, int ROWS, int NX = 0>
+template <int G, int CPT, int ROWS, int NX = 0, class WT = float>
 static hipError_t dispatch_area_full_g(const FwdArgs& a, hipStream_t s)
 {
-    return (a.flags & SOT_FLAG_SQUARE) ? launch_area_full<G, CPT, ROWS, true, NX>(a, s) : launch_area_full<G, CPT, ROWS, false, NX>(a, s);
+    return (a.flags & SOT_FLAG_SQUARE) ? launch_area_full<G, CPT, ROWS, true, NX, WT>(a, s) : launch_area_full<G, CPT, ROWS, false, NX, WT>(a, s);
+}
+
+// 512 / 1024 / 2048 / 4096 bins on shared positions: the geometries of the merge-free kernel for either element type (declared in sot_launch.hpp)
+template <class WT>
+hipError_t dispatch_area_full_pow2(const FwdArgs& a, hipStream_t s)
+{
+    switch (a.n) {
+        case 512: return dispatch_area_full_g<64, 8, 4, 0, WT>(a, s);
+        case 1024: return dispatch_area_full_g<128, 8, 2, 0, WT>(a, s);
+        case 2048: return dispatch_area_full_g<256, 8, 1, 0, WT>(a, s);
+        case 4096: return dispatch_area_full_g<512, 8, 1, 0, WT>(a, s);
+        default: return hipErrorInvalidConfiguration;
+    }
 }
 
 template <int CPT, int ROWS, bool SQ, int N>
@@ -682,19 +676,32 @@ static hipError_t dispatch_area_half(const FwdArgs& a, hipStream_t s)
     return (a.flags & SOT_FLAG_SQUARE) ? launch_area_half<CPT, ROWS, true, N>(a, s) : launch_area_half<CPT, ROWS, false, N>(a, s);
 }
 
-template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool RP = false>
+template <int G, int CPT, int ROWS, int PM, bool LIM, bool SQ, int NX, bool RP = false, class WT = float>
 static hipError_t launch_forward_full(const FwdArgs& a, hipStream_t s)
 {
     constexpr FullLayout L = full_layout<G, CPT, ROWS, false, NX>();
-    return launch_persistent_profiled<sot_forward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, RP>>(a, sizeof(float) * (size_t)L.total, (a.B + ROWS - 1) / ROWS,
-                                                                                               ROWS * G, s);
+    return launch_persistent_profiled<sot_forward_full_kernel<G, CPT, ROWS, PM, LIM, SQ, NX, RP, WT>>(a, sizeof(float) * (size_t)L.total, (a.B + ROWS - 1) / ROWS,
+                                                                                                   ROWS * G, s);
 }
 
-template <int G, int CPT, int ROWS, int NX = 0>
+template <int G, int CPT, int ROWS, int NX = 0, class WT = float>
 static hipError_t dispatch_forward_full_g(int pm, const FwdArgs& a, hipStream_t s)
 {
     static_assert(sizeof(float) * (size_t)full_layout<G, CPT, ROWS, false, NX>().total <= kLdsLimit, "workgroup fits one CU's LDS");
-    return with_mode(pm, a.flags, [&](auto md) { using M = decltype(md); return launch_forward_full<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX>(a, s); });
+    return with_mode(pm, a.flags, [&](auto md) { using M = decltype(md); return launch_forward_full<G, CPT, ROWS, M::PM, M::LIM, M::SQ, NX, false, WT>(a, s); });
+}
+
+// 512 / 1024 / 2048 / 4096 bins on shared positions: the geometries of the merge kernel for either element type (declared in sot_launch.hpp)
+template <class WT>
+hipError_t dispatch_forward_full_pow2(int pm, const FwdArgs& a, hipStream_t s)
+{
+    switch (a.n) {
+        case 512: return dispatch_forward_full_g<64, 8, 4, 0, WT>(pm, a, s);
+        case 1024: return dispatch_forward_full_g<128, 8, 2, 0, WT>(pm, a, s);
+        case 2048: return dispatch_forward_full_g<256, 8, 1, 0, WT>(pm, a, s);
+        case 4096: return dispatch_forward_full_g<512, 8, 1, 0, WT>(pm, a, s);
+        default: return hipErrorInvalidConfiguration;
+    }
 }
 
 // Per-row positions with handed-over permutations on the compile-time geometries of 2048- / 1024- / 512-point rows, ONE row per workgroup (round 6).

@@ -1,5 +1,6 @@
 // sot_hip.hip -- MI355X (gfx950) C ABI of the 1-D spectral optimal-transport loss: the small kernels (position plan, batch mean,
-// sorts), launch setup, the routing of a call to its row kernel (run_forward / run_backward) and the extern "C" entry points.
+// sorts), launch setup, the routing of a call to its row kernel (run_forward / run_backward, for float32 and bfloat16 rows alike), the
+// bodies of the row-weight calls that the float32 and the _bf16 entry points share (forward_call ...) and the extern "C" entry points.
 // The row kernels are in sot_rows.hpp (generic) and sot_full_fwd.hpp / sot_full_bwd.hpp (compile-time geometries); build.py lists the objects.
 #include "sot_launch.hpp"
 
@@ -485,9 +486,12 @@ int setup_launch(const sot_problem* pr, bool with_grad, void* workspace, size_t 
     return SOT_OK;
 }
 
+// wt == Elem::bf16 (both routers): pr->x / pr->y are 16-bit rows and bf16_native(pr) holds (the caller's business: bf16_rows_call), which
+// makes `full` true below; nothing ahead of the dispatch follows x or y, and the route predicates are computed once for both element types.
 int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, float* Q, float* U, float* V,
-                       bool quant, void* workspace, size_t workspace_bytes, void* stream, const MeanTail* mean_tail)
+                       bool quant, void* workspace, size_t workspace_bytes, void* stream, const MeanTail* mean_tail, Elem wt)
 {
+    const bool h = wt == Elem::bf16;
     Launch l;
     int rc = setup_launch(pr, false, workspace, workspace_bytes, stream, &l);
     if (rc != SOT_OK) return rc;
@@ -505,10 +509,12 @@ int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, fl
     // compile-time-length kernel with a position copy of its own per row (sot_full_fwd.hpp: RP)
     const bool full_rp = l.rowpos && l.a.perm_in != nullptr && !quant && (pr->n == 2048 || pr->n == 1024 || pr->n == 512) && pr->m == pr->n && l.vec && (pr->flags & SOT_FLAG_REQUIRE_SORT) &&
                    (reinterpret_cast<uintptr_t>(l.a.perm_in) & 15) == 0 && !(pr->flags & (SOT_FLAG_PRENORMALIZED | SOT_FLAG_NO_SPECIALIZE));
+    if (h && !full) return SOT_ERR_BAD_SHAPE;   // (never: 16-bit rows have no other kernel)
     if (full_rp) return launch_status(dispatch_forward_full_rowpos(l.pm, l.a, l.s));
     // p = 1 on one grid shared by both measures, no cutoff: the merge-free kernel (sot_full_fwd.hpp: sot_area_full_kernel)
     const bool area = (full || full_rt) && l.pm == 1 && (pr->flags & SOT_FLAG_SAME_GRID) && !(pr->flags & (SOT_FLAG_LIMIT_Q | SOT_FLAG_NO_AREA));
-    const hipError_t e = area       ? (full ? dispatch_area_full(l.a, l.s) : dispatch_area_full_rt(l.a, l.s))
+    const hipError_t e = h          ? (area ? dispatch_area_full_pow2<uint16_t>(l.a, l.s) : dispatch_forward_full_pow2<uint16_t>(l.pm, l.a, l.s))
+                         : area     ? (full ? dispatch_area_full(l.a, l.s) : dispatch_area_full_rt(l.a, l.s))
                          : full     ? dispatch_forward_full(l.pm, l.a, l.s)
                          : full_rt  ? dispatch_forward_full_rt(l.pm, l.a, l.s)
                          : l.rowpos ? dispatch_forward<true>(l.cfg, quant, l.pm, l.vec, l.a, l.lds, l.want, l.block, l.s)
@@ -520,15 +526,16 @@ int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, fl
 // runs the forward kernel otherwise.  grad_row == nullptr: an upstream gradient of 1 for every row.
 int run_backward(const sot_problem* pr, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* gx,
                         float* gy, void* workspace, size_t workspace_bytes, void* stream, float* row_loss_out, bool* fused,
-                        const MeanTail* mean_tail)
+                        const MeanTail* mean_tail, Elem wt, const float* rescale)
 {
+    const bool h = wt == Elem::bf16;
     Launch l;
     int rc = setup_launch(pr, true, workspace, workspace_bytes, stream, &l);
     if (rc != SOT_OK) return rc;
     if (fused) *fused = false;
     if (pr->B == 0 || (gx == nullptr && gy == nullptr)) return SOT_OK;
     BwdArgs b{};
-    b.f = l.a; b.grad_row = grad_row; b.grad_row_stride = grad_row_stride; b.grad_scale = grad_scale; b.gx = gx; b.gy = gy;
+    b.f = l.a; b.grad_row = grad_row; b.grad_row_stride = grad_row_stride; b.grad_scale = grad_scale; b.gx = gx; b.gy = gy; b.rescale = rescale;
     // row lengths with a compile-time kernel take it (as in run_forward)
     const bool aligned16 = l.vec && (gx == nullptr || (reinterpret_cast<uintptr_t>(gx) & 15) == 0) &&
                            (gy == nullptr || (reinterpret_cast<uintptr_t>(gy) & 15) == 0);
@@ -549,7 +556,9 @@ int run_backward(const sot_problem* pr, const float* grad_row, int64_t grad_row_
     // float32 tie-order artefact
     const bool area = full && gx == nullptr && l.pm == 1 && area_train_supports(pr->n) && (pr->flags & SOT_FLAG_SAME_GRID) && (pr->flags & SOT_FLAG_TIE_FREE_GRADIENT) &&
                       !(pr->flags & (SOT_FLAG_LIMIT_Q | SOT_FLAG_NO_AREA));
-    const hipError_t e = area       ? dispatch_area_train(b, l.s)
+    if (h && (!full || area)) return SOT_ERR_BAD_SHAPE;   // (never: 16-bit rows have no other kernel)
+    const hipError_t e = h          ? dispatch_backward_full_pow2<uint16_t>(l.pm, b, l.s)
+                         : area     ? dispatch_area_train(b, l.s)
                          : full_rp  ? dispatch_backward_full_rowpos(l.pm, b, l.s)
                          : full     ? dispatch_backward_full(l.pm, b, l.s)
                          : full_rt  ? dispatch_backward_full_rt(l.pm, b, l.s)
@@ -577,6 +586,70 @@ bool profile_take(hipEvent_t* start, hipEvent_t* stop)
     t_prof_armed = -1;
     *start = g_prof_start[slot]; *stop = g_prof_stop[slot];
     return true;
+}
+
+// The four row-weight calls, each ONE body for both element types: the argument checks of the entry point, then `body` -- on the caller's
+// problem for float32, through bf16_rows_call (sot_bf16.hip) for bfloat16, which hands it the 16-bit rows where the native kernels take
+// them and float32 images of them otherwise.
+template <class Body>
+static inline int rows_call(Elem wt, const sot_problem* prob, bool backward, void* gx, void* gy, const float* rescale, void* workspace,
+                            size_t workspace_bytes, void* stream, const Body& body)
+{
+    if (wt == Elem::f32) return body(wt, prob, static_cast<float*>(gx), static_cast<float*>(gy), nullptr, workspace, workspace_bytes);
+    return bf16_rows_call(prob, backward, static_cast<uint16_t*>(gx), static_cast<uint16_t*>(gy), rescale, workspace, workspace_bytes, stream, std::cref(body));
+}
+
+int forward_call(Elem wt, const sot_problem* prob, float* row_loss, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
+    return rows_call(wt, prob, false, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream,
+                     [&](Elem t, const sot_problem* pr, float*, float*, const float*, void* ws, size_t wsb) {
+                         return run_forward(pr, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, ws, wsb, stream, nullptr, t);
+                     });
+}
+
+int loss_call(Elem wt, const sot_problem* prob, float* row_loss, double denom, int apply_hinge, float hinge_threshold, float* mean_out, double* sum_out,
+              uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
+    if (mean_out == nullptr && sum_out == nullptr) return SOT_ERR_NULL_POINTER;
+    if (prob != nullptr && prob->B == 0) return SOT_ERR_BAD_SHAPE;  // the mean of zero rows is undefined
+    const MeanTail mt = make_tail(completion_counters, denom, apply_hinge, hinge_threshold, mean_out, sum_out);
+    return rows_call(wt, prob, false, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream,
+                     [&](Elem t, const sot_problem* pr, float*, float*, const float*, void* ws, size_t wsb) {
+                         const int rc = run_forward(pr, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, ws, wsb, stream,
+                                                    completion_counters ? &mt : nullptr, t);
+                         if (rc != SOT_OK || completion_counters != nullptr) return rc;
+                         return sot_w1d_reduce_mean(row_loss, pr->B, denom, apply_hinge, hinge_threshold, mean_out, sum_out, stream);
+                     });
+}
+
+int backward_call(Elem wt, const sot_problem* prob, const float* grad_row, int64_t grad_row_stride, float grad_scale, void* grad_x, void* grad_y,
+                  const float* rescale, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (grad_row_stride != 0 && grad_row_stride != 1) return SOT_ERR_BAD_SHAPE;
+    return rows_call(wt, prob, true, grad_x, grad_y, rescale, workspace, workspace_bytes, stream,
+                     [&](Elem t, const sot_problem* pr, float* gx, float* gy, const float* rs, void* ws, size_t wsb) {
+                         return run_backward(pr, grad_row, grad_row_stride, grad_scale, gx, gy, ws, wsb, stream, nullptr, nullptr, nullptr, t, rs);
+                     });
+}
+
+int loss_and_grad_call(Elem wt, const sot_problem* prob, float* row_loss, double denom, float* mean_out, double* sum_out, float grad_scale, void* grad_y,
+                       uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (prob == nullptr) return SOT_ERR_NULL_POINTER;
+    if (prob->B == 0) return SOT_ERR_BAD_SHAPE;  // the mean of zero rows is undefined
+    if (row_loss == nullptr || grad_y == nullptr || (mean_out == nullptr && sum_out == nullptr)) return SOT_ERR_NULL_POINTER;
+    const MeanTail mt = make_tail(completion_counters, denom, 0, 0.0f, mean_out, sum_out);
+    const MeanTail* tail = completion_counters ? &mt : nullptr;
+    return rows_call(wt, prob, true, nullptr, grad_y, nullptr, workspace, workspace_bytes, stream,
+                     [&](Elem t, const sot_problem* pr, float*, float* gy, const float*, void* ws, size_t wsb) {
+                         bool fused = false;   // the y-only full-row kernel writes the row losses on its walk; behind every other backward the forward kernel runs
+                         int rc = run_backward(pr, nullptr, 0, grad_scale, nullptr, gy, ws, wsb, stream, row_loss, &fused, tail, t);
+                         if (rc == SOT_OK && !fused) rc = run_forward(pr, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, ws, wsb, stream, tail, t);
+                         if (rc != SOT_OK || tail != nullptr) return rc;  // (with a tail the kernel that wrote the row losses reduced them)
+                         return sot_w1d_reduce_mean(row_loss, pr->B, denom, 0, 0.0f, mean_out, sum_out, stream);
+                     });
 }
 }  // namespace sot
 
@@ -657,8 +730,7 @@ int sot_prepare_unit_positions(const float* xpos, const float* ypos, int32_t n, 
 
 int sot_w1d_forward(const sot_problem* prob, float* row_loss, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
-    return sot::run_forward(prob, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, stream);
+    return sot::forward_call(sot::Elem::f32, prob, row_loss, workspace, workspace_bytes, stream);
 }
 
 int sot_w1d_quantiles(const sot_problem* prob, float* uq, float* vq, float* Q, float* U, float* V, void* workspace,
@@ -682,34 +754,14 @@ int sot_w1d_reduce_mean(const float* row_loss, int64_t B, double denom, int appl
 int sot_w1d_backward(const sot_problem* prob, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* grad_x,
                      float* grad_y, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (grad_row_stride != 0 && grad_row_stride != 1) return SOT_ERR_BAD_SHAPE;
-    return sot::run_backward(prob, grad_row, grad_row_stride, grad_scale, grad_x, grad_y, workspace, workspace_bytes, stream);
-}
-
-static inline sot::MeanTail make_tail(uint32_t* counters, double denom, int apply_hinge, float hinge, float* mean_out, double* sum_out)
-{
-    sot::MeanTail mt{};
-    mt.counters = counters; mt.denom = denom; mt.apply_hinge = apply_hinge; mt.hinge = hinge; mt.mean_out = mean_out; mt.sum_out = sum_out;
-    return mt;
+    return sot::backward_call(sot::Elem::f32, prob, grad_row, grad_row_stride, grad_scale, grad_x, grad_y, nullptr, workspace, workspace_bytes, stream);
 }
 
 int sot_w1d_loss_and_grad(const sot_problem* prob, float* row_loss, double denom, float* mean_out, double* sum_out, float grad_scale,
                           float* grad_y, uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (prob == nullptr) return SOT_ERR_NULL_POINTER;
-    if (prob->B == 0) return SOT_ERR_BAD_SHAPE;  // the mean of zero rows is undefined
-    if (row_loss == nullptr || grad_y == nullptr || (mean_out == nullptr && sum_out == nullptr)) return SOT_ERR_NULL_POINTER;
-    const sot::MeanTail mt = make_tail(completion_counters, denom, 0, 0.0f, mean_out, sum_out);
-    const sot::MeanTail* tail = completion_counters ? &mt : nullptr;
-    bool fused = false;
-    int rc = sot::run_backward(prob, nullptr, 0, grad_scale, nullptr, grad_y, workspace, workspace_bytes, stream, row_loss, &fused, tail);
-    if (rc != SOT_OK) return rc;
-    if (!fused) {
-        rc = sot::run_forward(prob, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes, stream, tail);
-        if (rc != SOT_OK) return rc;
-    }
-    if (tail != nullptr) return SOT_OK;  // the kernel that wrote the row losses reduced them
-    return sot_w1d_reduce_mean(row_loss, prob->B, denom, 0, 0.0f, mean_out, sum_out, stream);
+    return sot::loss_and_grad_call(sot::Elem::f32, prob, row_loss, denom, mean_out, sum_out, grad_scale, grad_y, completion_counters, workspace,
+                                   workspace_bytes, stream);
 }
 
 int sot_scale_inplace(float* data, int64_t count, const float* scalar, void* stream)
@@ -727,14 +779,8 @@ int sot_scale_inplace(float* data, int64_t count, const float* scalar, void* str
 int sot_w1d_loss(const sot_problem* prob, float* row_loss, double denom, int apply_hinge, float hinge_threshold, float* mean_out,
                  double* sum_out, uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (prob != nullptr && prob->B > 0 && row_loss == nullptr) return SOT_ERR_NULL_POINTER;
-    if (mean_out == nullptr && sum_out == nullptr) return SOT_ERR_NULL_POINTER;
-    if (prob != nullptr && prob->B == 0) return SOT_ERR_BAD_SHAPE;  // the mean of zero rows is undefined
-    const sot::MeanTail mt = make_tail(completion_counters, denom, apply_hinge, hinge_threshold, mean_out, sum_out);
-    const int rc = sot::run_forward(prob, row_loss, nullptr, nullptr, nullptr, nullptr, nullptr, false, workspace, workspace_bytes,
-                                    stream, completion_counters ? &mt : nullptr);
-    if (rc != SOT_OK || completion_counters != nullptr) return rc;
-    return sot_w1d_reduce_mean(row_loss, prob->B, denom, apply_hinge, hinge_threshold, mean_out, sum_out, stream);
+    return sot::loss_call(sot::Elem::f32, prob, row_loss, denom, apply_hinge, hinge_threshold, mean_out, sum_out, completion_counters, workspace,
+                          workspace_bytes, stream);
 }
 
 int sot_w1d_position_grad(const sot_problem* prob, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* grad_xpos,

@@ -4,6 +4,7 @@
 #pragma once
 #include "sot_host.hpp"
 #include "sot_rows.hpp"
+#include <functional>
 
 namespace sot {
 
@@ -46,6 +47,14 @@ static inline int validate(const sot_problem* pr)
 }
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the batch mean out of the row kernel's last workgroup (sot_w1d_loss, sot_w1d_loss_and_grad): the one place a MeanTail is filled
+static inline MeanTail make_tail(uint32_t* counters, double denom, int apply_hinge, float hinge, float* mean_out, double* sum_out)
+{
+    MeanTail mt{};
+    mt.counters = counters; mt.denom = denom; mt.apply_hinge = apply_hinge; mt.hinge = hinge; mt.mean_out = mean_out; mt.sum_out = sum_out;
+    return mt;
+}
 
 struct WsLayout { size_t sx, sy, px, py, ident, total; };
 // the permutation image of a per-row-position call (setup_launch: the pre-sort kernel's output when the caller passes no row_perm_out)
@@ -163,23 +172,46 @@ hipError_t dispatch_backward_full(int pm, const BwdArgs& b, hipStream_t s);
 hipError_t dispatch_backward_full_rowpos(int pm, const BwdArgs& b, hipStream_t s);   // per-row positions through handed-over permutations, 2048-point rows (round 6)
 hipError_t dispatch_area_train(const BwdArgs& b, hipStream_t s);
 bool area_train_supports(int n);
+// The geometry tables of 512 / 1024 / 2048 / 4096 bins on shared positions, ONE per route family for every element type WT of the weight rows
+// (the backward's gradient rows have the same type).  Defined in sot_full_fwd.hpp / sot_full_bwd.hpp; the three float32 switches above fall
+// through to <float>, sot_bf16.hip (area, forward) and sot_bf16_bwd.hip (backward) instantiate <uint16_t>: a kernel is compiled into the
+// object that instantiates its table.
+template <class WT> hipError_t dispatch_area_full_pow2(const FwdArgs& a, hipStream_t s);
+template <class WT> hipError_t dispatch_forward_full_pow2(int pm, const FwdArgs& a, hipStream_t s);
+template <class WT> hipError_t dispatch_backward_full_pow2(int pm, const BwdArgs& b, hipStream_t s);
 // sot_full_rt_fwd.hip, sot_full_rt_bwd.hip
 hipError_t dispatch_forward_full_rt(int pm, const FwdArgs& a, hipStream_t s);
 hipError_t dispatch_area_full_rt(const FwdArgs& a, hipStream_t s);
 hipError_t dispatch_backward_full_rt(int pm, const BwdArgs& b, hipStream_t s);
-// sot_hip.hip
+// sot_hip.hip.  Elem: the element type of the weight rows pr->x / pr->y in memory (and, for the backward, of the gradient rows gx / gy, which
+// then point at 16-bit elements).  A bf16 problem reaches the two routers only where bf16_native(pr, with the backward's buffers) holds; they
+// pick the 16-bit instantiation of the route the float32 call takes.  rescale: the fix-up mode of the 16-bit y-only kernel (BwdArgs::rescale).
+enum class Elem { f32, bf16 };
 int launch_prepare(const float* xpos, const float* ypos, int n, int m, float* sx, float* sy, int* px, int* py, int* ident,
                    hipStream_t s, bool unit = false);
 int setup_launch(const sot_problem* pr, bool with_grad, void* workspace, size_t workspace_bytes, void* stream, Launch* out);
 int run_forward(const sot_problem* pr, float* row_loss, float* uq, float* vq, float* Q, float* U, float* V, bool quant,
-                void* workspace, size_t workspace_bytes, void* stream, const MeanTail* mean_tail = nullptr);
+                void* workspace, size_t workspace_bytes, void* stream, const MeanTail* mean_tail = nullptr, Elem wt = Elem::f32);
 int run_backward(const sot_problem* pr, const float* grad_row, int64_t grad_row_stride, float grad_scale, float* gx, float* gy,
                  void* workspace, size_t workspace_bytes, void* stream, float* row_loss_out = nullptr, bool* fused = nullptr,
-                 const MeanTail* mean_tail = nullptr);
-// sot_bf16.hip (bfloat16 rows): the row conversions and the native route's condition on the problem; sot_bf16_bwd.hip: the typed backward
+                 const MeanTail* mean_tail = nullptr, Elem wt = Elem::f32, const float* rescale = nullptr);
+// the bodies of sot_w1d_forward / _loss / _backward / _loss_and_grad and of their _bf16 twins (gx, gy: rows of wt; rescale: bf16 only)
+int forward_call(Elem wt, const sot_problem* prob, float* row_loss, void* workspace, size_t workspace_bytes, void* stream);
+int loss_call(Elem wt, const sot_problem* prob, float* row_loss, double denom, int apply_hinge, float hinge_threshold, float* mean_out, double* sum_out,
+              uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream);
+int backward_call(Elem wt, const sot_problem* prob, const float* grad_row, int64_t grad_row_stride, float grad_scale, void* grad_x, void* grad_y,
+                  const float* rescale, void* workspace, size_t workspace_bytes, void* stream);
+int loss_and_grad_call(Elem wt, const sot_problem* prob, float* row_loss, double denom, float* mean_out, double* sum_out, float grad_scale, void* grad_y,
+                       uint32_t* completion_counters, void* workspace, size_t workspace_bytes, void* stream);
+// sot_bf16.hip (bfloat16 rows): the row conversions, the native routes' condition, the workspace of a typed call, and the typed call itself:
+// `call` on the 16-bit rows where the native kernels take them, else on float32 images in the workspace (widen, the float32 call, narrow).
 int launch_rows_bf16_to_f32(const uint16_t* src, int64_t B, int n, int64_t ss, float* dst, int64_t ds, hipStream_t s);
 int launch_rows_f32_to_bf16(const float* src, int64_t B, int n, int64_t ss, uint16_t* dst, int64_t ds, hipStream_t s);
-bool bf16_native(const sot_problem* pr);
+bool bf16_native(const sot_problem* pr, bool backward);
+size_t bf16_workspace_bytes(const sot_problem* pr, bool backward, bool want_x, bool want_y);
+using RowsCall = std::function<int(Elem wt, const sot_problem* pr, float* gx, float* gy, const float* rescale, void* workspace, size_t workspace_bytes)>;
+int bf16_rows_call(const sot_problem* pr, bool backward, uint16_t* gx, uint16_t* gy, const float* rescale, void* workspace, size_t workspace_bytes,
+                   void* stream, const RowsCall& call);
 // sot_csr.hip
 int run_forward_csr(const float* xw, const float* xp, const int64_t* xoff, int64_t x_nnz, const float* yw, const float* yp,
                     const int64_t* yoff, int64_t y_nnz, int64_t B, int max_n, int max_m, float p, uint32_t flags, float* row_loss,

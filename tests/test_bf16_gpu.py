@@ -180,7 +180,7 @@ def _native_reference(n, G, mode):
     return nat.forward_rows(x16.float(), y16.float(), pos, pos2, p, flags)
 
 
-# n, G = threads per row, ROWS per workgroup: the geometries of csrc/sot_bf16.hip (dispatch_area_full_bf16 / dispatch_forward_full_bf16)
+# n, G = threads per row, ROWS per workgroup: the geometries of csrc/sot_full_fwd.hpp (dispatch_area_full_pow2 / dispatch_forward_full_pow2)
 NATIVE = [(512, 64, 4), (1024, 128, 2), (2048, 256, 1), (4096, 512, 1)]
 
 

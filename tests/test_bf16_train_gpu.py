@@ -110,7 +110,7 @@ def typed_loss_and_grad(nat, x16, y16, xpos, ypos, p, flags, workspace_bytes=Non
 
 
 # ------------------------------------------------------------------------------------------------------------- 1. native backward
-# n, G = threads per row, rows per workgroup of the both-gradient / of the y-only kernel (csrc/sot_bf16_bwd.hip: dispatch_backward_full_bf16)
+# n, G = threads per row, rows per workgroup of the both-gradient / of the y-only kernel (csrc/sot_full_bwd.hpp: dispatch_backward_full_pow2)
 NATIVE = [(512, 64, 4, 4), (1024, 128, 2, 2), (2048, 256, 1, 2), (4096, 512, 1, 1)]
 
 

@@ -15,7 +15,7 @@ Per line of W1D / STFT_FAR and per test of the other entry points, for each mode
 
 Three rows cannot reach a route behind a batch threshold: at 257 bins the half-wave kernel serves batches from 40960 rows, which at this
 stride would be 160 TiB, so the 257-bin line runs the full kernel and the half-wave family is represented by the merge-free 129-bin kernel,
-which has no threshold (csrc/sot_full_fwd.hip:17).  The one-wave-per-frame STFT kernels (from 3072 frames / 1024 frame groups) are out of a
+which has no threshold (csrc/sot_full_fwd.hip: dispatch_area_full).  The one-wave-per-frame STFT kernels (from 3072 frames / 1024 frame groups) are out of a
 three-clip batch's reach for the same reason; test_dense_* below takes them across 2^31 elements of their outputs instead.
 
 test_dense_*: DENSE buffers that themselves cross 2^31 elements need their real size: the smallest batch with B * n > 2^31.  The ABI refuses
@@ -136,16 +136,16 @@ FWD, RT, BWD, HIP, PICK = rl.FWD, rl.RT, rl.BWD, rl.HIP, rl.PICK
 Line = collections.namedtuple("Line", "id n m rowpos flags area cite")
 # id, n, m, per-row positions, extra flags, merge-free?, the dispatch lines three aligned rows take: forward; backward (both gradients); training form
 W1D = [
-    Line("merge2048", 2048, 2048, False, 0, False, FWD + ":68 <256, 8, 1>; " + BWD + ":37 <256, 8, 1, 0, 1>; " + HIP + ":542 -> " + BWD + ":36"),
-    Line("merge1025", 1025, 1025, False, 0, False, FWD + ":89 <128, 9, 2, 1025> (3 rows < 6144: two waves per row); " + BWD + ":53; " + HIP + ":542 -> " + BWD + ":52"),
-    Line("merge_free2048", 2048, 2048, False, 0, True, FWD + ":13 dispatch_area_full_g<256, 8, 1>; " + BWD + ":37; " + HIP + ":550 area -> " + BWD + ":13 dispatch_area_train_g<256, 8, 1> "
+    Line("merge2048", 2048, 2048, False, 0, False, FWD + ": dispatch_forward_full_pow2 (sot_full_fwd.hpp), <256, 8, 1>; " + BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp), <256, 8, 1, 0, 1>; " + HIP + ": run_backward -> the y-only kernel of the same table"),
+    Line("merge1025", 1025, 1025, False, 0, False, FWD + ": dispatch_forward_full, <128, 9, 2, 1025> (3 rows < 6144: two waves per row); " + BWD + ": dispatch_backward_full; " + HIP + ": run_backward -> its y-only kernel"),
+    Line("merge_free2048", 2048, 2048, False, 0, True, FWD + ": dispatch_area_full_pow2 (sot_full_fwd.hpp), dispatch_area_full_g<256, 8, 1>; " + BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp); " + HIP + ": run_backward, area -> " + BWD + ": dispatch_area_train, dispatch_area_train_g<256, 8, 1> "
          "(SOT_FLAG_TIE_FREE_GRADIENT; the far rows are 16-byte aligned, so `full` holds as for the dense ones)"),
-    Line("half_wave129", 129, 129, False, 0, True, FWD + ":17 dispatch_area_half<5, 8, 129> (every batch size); " + BWD + ":39 <64, 3, 4, 129>"),
-    Line("full257", 257, 257, False, 0, False, FWD + ":80 <64, 5, 4, 257> (3 rows < 40960: not the half-wave kernel of :79); " + BWD + ":44"),
+    Line("half_wave129", 129, 129, False, 0, True, FWD + ": dispatch_area_full, dispatch_area_half<5, 8, 129> (every batch size); " + BWD + ": dispatch_backward_full, <64, 3, 4, 129>"),
+    Line("full257", 257, 257, False, 0, False, FWD + ": dispatch_forward_full, <64, 5, 4, 257> (3 rows < 40960: not the half-wave kernel); " + BWD + ": dispatch_backward_full"),
     Line("rt1500", 1500, 1500, False, 0, False, RT + ":15 <192, 8, 1, -1>; csrc/sot_full_rt_bwd.hip:20 <192, 8, 1, -1>"),
     Line("gen300x411", 300, 411, False, rl.NS, False, PICK + " (64, 8), n != m, forward and backward"),
-    Line("rp2048", 2048, 2048, True, 0, False, HIP + ":384 launch_rowpos_sort; " + HIP + ":506 -> dispatch_forward_full_rowpos_g<256>; " + HIP + ":540 -> dispatch_backward_full_rowpos_g<256>"),
-    Line("rp700", 700, 700, True, 0, False, HIP + ":384; " + HIP + ":514 dispatch_forward<true>, " + HIP + ":556 dispatch_backward<true>, " + PICK + " (128, 12)"),
+    Line("rp2048", 2048, 2048, True, 0, False, HIP + ": launch_rowpos_sort; " + HIP + ": run_forward -> dispatch_forward_full_rowpos_g<256>; " + HIP + ": run_backward -> dispatch_backward_full_rowpos_g<256>"),
+    Line("rp700", 700, 700, True, 0, False, HIP + ": launch_rowpos_sort; " + HIP + ": run_forward, dispatch_forward<true>, " + HIP + ": run_backward, dispatch_backward<true>, " + PICK + " (128, 12)"),
 ]
 W1D_BY_ID = {ln.id: ln for ln in W1D}
 
@@ -203,7 +203,7 @@ def test_w1d_forward_backward_loss_and_training_form(far, name):
 
 @pytest.mark.parametrize("rowpos", [False, True], ids=["shared", "rowpos"])
 def test_quantiles_and_their_backward(far, rowpos):
-    """sot_w1d_quantiles, sot_w1d_quantiles_backward at 300 points: csrc/sot_hip.hip:667 run_forward(quant) and csrc/sot_quantgrad.hip:239, pick_cfg (64, 8)"""
+    """sot_w1d_quantiles, sot_w1d_quantiles_backward at 300 points: csrc/sot_hip.hip: sot_w1d_quantiles, run_forward(quant) and csrc/sot_quantgrad.hip:239, pick_cfg (64, 8)"""
     nat = native()
     lib, B, n, m = nat.load(), ROWS, 300, 300
     case = rl.C("quant300", "quant", n, 0, 0, "", rowpos=rowpos)
@@ -321,8 +321,8 @@ def test_forward_csr_with_offsets_past_2_31(far):
         assert same_bits(want[0::2], dense), "the five-row dense call differs from the three true rows alone"
 
 
-@pytest.mark.parametrize("n,cite", [(100, HIP + ":770 launch_segmented_sort_wave<2>"), (2048, HIP + ":773 launch_segmented_sort_wave<32>"),
-                                    (3000, HIP + ":786 sot_segmented_sort_kernel")], ids=["100", "2048", "3000"])
+@pytest.mark.parametrize("n,cite", [(100, HIP + ": sot_segmented_sort, launch_segmented_sort_wave<2>"), (2048, HIP + ": sot_segmented_sort, launch_segmented_sort_wave<32>"),
+                                    (3000, HIP + ": sot_segmented_sort, sot_segmented_sort_kernel")], ids=["100", "2048", "3000"])
 def test_segmented_sort(far, n, cite):
     nat = native()
     keys, _ = rk.make_positions(ROWS, n, 100 + n, device())
@@ -529,8 +529,8 @@ def free_memory():
 
 @pytest.mark.parametrize("tie_free", [False, True], ids=["merge_walk", "merge_free"])
 def test_dense_loss_and_grad_2048(tie_free):
-    """sot_w1d_loss_and_grad, p = 1 on one grid, n = m = 2048, B = 2^20 + 1: grad_y has 2^31 + 2048 elements (csrc/sot_hip.hip:542 ->
-    csrc/sot_full_bwd.hip:36, and with SOT_FLAG_TIE_FREE_GRADIENT :550 -> csrc/sot_full_bwd.hip:13).  Both kernels are chosen by the row length
+    """sot_w1d_loss_and_grad, p = 1 on one grid, n = m = 2048, B = 2^20 + 1: grad_y has 2^31 + 2048 elements (csrc/sot_hip.hip: run_backward ->
+    csrc/sot_full_bwd.hpp: dispatch_backward_full_pow2, and with SOT_FLAG_TIE_FREE_GRADIENT `area` -> csrc/sot_full_bwd.hip: dispatch_area_train).  Both kernels are chosen by the row length
     alone, so the last rows as a call of their own are held bit for bit."""
     from oracle import sot_oracle as so
     nat = native()
@@ -593,7 +593,7 @@ def test_dense_backward_generic_300():
 
 
 def test_dense_segmented_sort_2048():
-    """sot_segmented_sort, n = 2048, keys only (indices = NULL, which the entry point allows), B = 2^20 + 1 (csrc/sot_hip.hip:773
+    """sot_segmented_sort, n = 2048, keys only (indices = NULL, which the entry point allows), B = 2^20 + 1 (csrc/sot_hip.hip: sot_segmented_sort,
     launch_segmented_sort_wave<32>, chosen by n alone)"""
     nat = native()
     n, B = 2048, rows_past_2_31(2048)

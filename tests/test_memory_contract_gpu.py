@@ -67,7 +67,7 @@ ALL, DENSE = ("A", "O", "S"), ("A", "O")
 # Every layout a line does not name here is held to A bit for bit.
 WAVE2_SCRATCH = ("csrc/sot_stft.hip:1387 launch_backward_spec_wave2 needs the scratch rows on 8-byte boundaries: with the workspace 4 bytes off the grid "
                  ":1524 stft_mag_backward_spec_kernel<10>, the slot kernel, serves the call (another FFT, another association)")
-TIE_FREE_2048 = ("csrc/sot_hip.hip:535 `full` needs backward_full_supports(2048, aligned16) and :550 `area` needs `full`: with rows 4 bytes off the grid "
+TIE_FREE_2048 = ("csrc/sot_hip.hip: run_backward, `full` needs backward_full_supports(2048, aligned16) and `area` needs `full`: with rows 4 bytes off the grid "
                  ":555 dispatch_backward_full_rt, the merge walk, serves the call -- SOT_FLAG_TIE_FREE_GRADIENT is a permission (include/sot_hip.h)")
 NOT_BITWISE = {"tiefree2048": {"O": TIE_FREE_2048, "S": TIE_FREE_2048}}     # for the lines taken over from tests/test_row_loop_gpu.py
 
@@ -88,32 +88,32 @@ CASES = [C(c.id, ENTRY_OF[c.family], c.family, c.n, c.m, c.rows, c.cite, c.lo, c
 FWD, HIP, PICK = rl.FWD, rl.HIP, rl.PICK
 CASES += [
     # the 129-bin full kernel below 8192 rows: tests/test_row_loop_gpu.py cannot force its second row; no second row is needed here
-    C("fwd129_full", "sot_w1d_forward", "fwd", 129, rows=4, cite=FWD + ":74 <64, 3, 4, 129>, below the 8192-row threshold", hi=rl.kHalf129Rows - 1),
+    C("fwd129_full", "sot_w1d_forward", "fwd", 129, rows=4, cite=FWD + ": dispatch_forward_full, <64, 3, 4, 129>, below the 8192-row threshold", hi=rl.kHalf129Rows - 1),
     # odd row lengths in the uint16 image: the y half of a row starts on an odd element, rows are 386 elements
-    C("rp129x257_odd_image", "sot_w1d_forward", "fwd_perm", 129, 257, rows=4, cite=HIP + ":447-459 row_perm_out / row_perm_in, " + PICK + " (64, 8)", rowpos=True),
-    C("rp129x257", "sot_w1d_forward", "fwd", 129, 257, rows=4, cite=HIP + ":384 launch_rowpos_sort, element-wise stores (n & 3 != 0)", rowpos=True),
+    C("rp129x257_odd_image", "sot_w1d_forward", "fwd_perm", 129, 257, rows=4, cite=HIP + ": setup_launch, row_perm_out / row_perm_in, " + PICK + " (64, 8)", rowpos=True),
+    C("rp129x257", "sot_w1d_forward", "fwd", 129, 257, rows=4, cite=HIP + ": launch_rowpos_sort, element-wise stores (n & 3 != 0)", rowpos=True),
     # beyond the pre-sort's domain: sot_workspace_bytes is 0 (csrc/sot_launch.hpp: rowpos_presort_runs), the call takes workspace = NULL, 0
-    C("rp2049_no_workspace", "sot_w1d_forward", "fwd", 2049, rows=1, cite=HIP + ":452 rowpos_presort_runs is false; " + PICK + " (1024, 8)", rowpos=True, no_workspace=True),
-    C("bwd_rp2049_no_workspace", "sot_w1d_backward", "bwd", 2049, rows=1, cite=HIP + ":452; " + PICK + " (1024, 8)", rowpos=True, no_workspace=True),
+    C("rp2049_no_workspace", "sot_w1d_forward", "fwd", 2049, rows=1, cite=HIP + ": setup_launch, rowpos_presort_runs is false; " + PICK + " (1024, 8)", rowpos=True, no_workspace=True),
+    C("bwd_rp2049_no_workspace", "sot_w1d_backward", "bwd", 2049, rows=1, cite=HIP + ": setup_launch; " + PICK + " (1024, 8)", rowpos=True, no_workspace=True),
     # shared positions planned inside the call: the workspace of ws_layout (csrc/sot_launch.hpp), exact
-    C("fwd_gen100_plan_in_workspace", "sot_w1d_forward", "fwd", 100, rows=4, cite=HIP + ":464-476 launch_prepare into the workspace", flags=NS, plan_in_workspace=True),
-    C("bwd513_plan_in_workspace", "sot_w1d_backward", "bwd", 513, rows=4, cite=HIP + ":464-476; " + rl.BWD + ":48", plan_in_workspace=True),
-    C("sort3000", "sot_segmented_sort", "sort", 3000, rows=1, cite=HIP + ":786 sot_segmented_sort_kernel (n > 2048: up to 1024 threads per row)"),
-    C("loss2048_two_kernels", ("sot_w1d_loss", "sot_w1d_reduce_mean"), "loss", 2048, rows=1, cite=HIP + ":735 forward, then sot_reduce_mean_kernel"),
-    C("loss513_hinge", ("sot_w1d_loss", "sot_w1d_reduce_mean"), "loss", 513, rows=4, cite=HIP + ":735, apply_hinge", hinge=0.01),
+    C("fwd_gen100_plan_in_workspace", "sot_w1d_forward", "fwd", 100, rows=4, cite=HIP + ": setup_launch, launch_prepare into the workspace", flags=NS, plan_in_workspace=True),
+    C("bwd513_plan_in_workspace", "sot_w1d_backward", "bwd", 513, rows=4, cite=HIP + ": setup_launch; " + rl.BWD + ": dispatch_backward_full", plan_in_workspace=True),
+    C("sort3000", "sot_segmented_sort", "sort", 3000, rows=1, cite=HIP + ": sot_segmented_sort, sot_segmented_sort_kernel (n > 2048: up to 1024 threads per row)"),
+    C("loss2048_two_kernels", ("sot_w1d_loss", "sot_w1d_reduce_mean"), "loss", 2048, rows=1, cite=HIP + ": loss_call, forward, then sot_reduce_mean_kernel"),
+    C("loss513_hinge", ("sot_w1d_loss", "sot_w1d_reduce_mean"), "loss", 513, rows=4, cite=HIP + ": loss_call, apply_hinge", hinge=0.01),
     C("mixed_fwd_rows_on_y", "sot_w1d_mixed_forward", "mixed_fwd", 257, 37, rows=4, cite="csrc/sot_mixed.hip:508 dispatch_mixed_g<0, 64, 8>; :474 plan in the workspace"),
     C("mixed_fwd_rows_on_x", "sot_w1d_mixed_forward", "mixed_fwd", 37, 1025, rows=2, cite="csrc/sot_mixed.hip:509 <0, 128, 12>", rows_on_x=True),
     C("mixed_bwd_rows_on_y", "sot_w1d_mixed_backward", "mixed_bwd", 257, 37, rows=4, cite="csrc/sot_mixed.hip:508 <1, 64, 8>"),
     C("mixed_bwd_rows_on_x", "sot_w1d_mixed_backward", "mixed_bwd", 37, 1025, rows=2, cite="csrc/sot_mixed.hip:509 <1, 128, 12>", rows_on_x=True),
     C("mixed_posgrad_rows_on_y", "sot_w1d_mixed_position_grad", "mixed_posgrad", 257, 37, rows=4, cite="csrc/sot_mixed.hip:491 <2, 64, 8>"),
     C("mixed_posgrad_rows_on_x", "sot_w1d_mixed_position_grad", "mixed_posgrad", 37, 1025, rows=2, cite="csrc/sot_mixed.hip:491 <2, 128, 12>", rows_on_x=True),
-    C("prepare300x411", "sot_prepare_positions", "prepare", 300, 411, cite=HIP + ":422 sot_prepare_positions_kernel<false>", layouts=DENSE),
-    C("prepare_unit1025", "sot_prepare_unit_positions", "prepare", 1025, cite=HIP + ":422 <true>", layouts=DENSE, unit=True),
-    C("reduce_mean5", "sot_w1d_reduce_mean", "reduce", 5, cite=HIP + ":675 sot_reduce_mean_kernel, fewer rows than lanes", layouts=DENSE),
-    C("reduce_mean4099", "sot_w1d_reduce_mean", "reduce", 4099, cite=HIP + ":675, 16-byte loads on aligned rows, scalar otherwise", layouts=DENSE, hinge=0.3),
-    C("scale3", "sot_scale_inplace", "scale", 3, cite=HIP + ":721 sot_scale_inplace_kernel, a tail shorter than one vector", layouts=DENSE),
-    C("scale4099", "sot_scale_inplace", "scale", 4099, cite=HIP + ":721, 16-byte access on aligned data, scalar otherwise", layouts=DENSE),
-    C("scale4099_by_one", "sot_scale_inplace", "scale", 4099, cite=HIP + ":721, scalar == 1: data is not touched", layouts=DENSE, scalar=1.0),
+    C("prepare300x411", "sot_prepare_positions", "prepare", 300, 411, cite=HIP + ": launch_prepare, sot_prepare_positions_kernel<false>", layouts=DENSE),
+    C("prepare_unit1025", "sot_prepare_unit_positions", "prepare", 1025, cite=HIP + ": launch_prepare, <true>", layouts=DENSE, unit=True),
+    C("reduce_mean5", "sot_w1d_reduce_mean", "reduce", 5, cite=HIP + ": sot_w1d_reduce_mean, sot_reduce_mean_kernel, fewer rows than lanes", layouts=DENSE),
+    C("reduce_mean4099", "sot_w1d_reduce_mean", "reduce", 4099, cite=HIP + ": sot_w1d_reduce_mean, 16-byte loads on aligned rows, scalar otherwise", layouts=DENSE, hinge=0.3),
+    C("scale3", "sot_scale_inplace", "scale", 3, cite=HIP + ": sot_scale_inplace, sot_scale_inplace_kernel, a tail shorter than one vector", layouts=DENSE),
+    C("scale4099", "sot_scale_inplace", "scale", 4099, cite=HIP + ": sot_scale_inplace, 16-byte access on aligned data, scalar otherwise", layouts=DENSE),
+    C("scale4099_by_one", "sot_scale_inplace", "scale", 4099, cite=HIP + ": sot_scale_inplace, scalar == 1: data is not touched", layouts=DENSE, scalar=1.0),
     C("column_sum9x300", "sot_column_sum", "colsum", 300, rows=None, cite="csrc/sot_posgrad.hip:237 run_column_sum"),
 ]
 

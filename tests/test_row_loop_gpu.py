@@ -43,8 +43,8 @@ pytestmark = pytest.mark.gpu
 
 kFwd1025OneWaveRows = 6144   # csrc/sot_full_fwd.hpp:28
 kRt1024OneWaveRows = 8192    # csrc/sot_full_fwd.hpp:29
-kHalf129Rows = 8192          # csrc/sot_full_fwd.hip:73
-kHalf257Rows = 40960         # csrc/sot_full_fwd.hip:79
+kHalf129Rows = 8192          # csrc/sot_full_fwd.hip: dispatch_forward_full
+kHalf257Rows = 40960         # csrc/sot_full_fwd.hip: dispatch_forward_full
 
 Case = collections.namedtuple("Case", "id family n m G rows cite B lo hi rowpos ends iters extra")
 
@@ -65,31 +65,31 @@ HIP = "csrc/sot_hip.hip"
 # serves the c-row calls.
 CASES = [
     # ---- compile-time forward (merge kernels; three modes) ----
-    C("fwd512", "fwd", 512, 64, 4, FWD + ":66 dispatch_forward_full_g<64, 8, 4>"),
-    C("fwd1024", "fwd", 1024, 128, 2, FWD + ":67 <128, 8, 2>"),
-    C("fwd2048", "fwd", 2048, 256, 1, FWD + ":68 <256, 8, 1>"),
-    C("fwd4096", "fwd", 4096, 512, 1, FWD + ":69 <512, 8, 1>"),
-    C("fwd8192", "fwd", 8192, 1024, 1, FWD + ":70 <1024, 8, 1>"),
-    C("fwd129_half", "fwd", 129, 32, 8, FWD + ":73 dispatch_forward_half<5, 8, 129> (HalfRowGeo, sot_full_fwd.hpp)", lo=kHalf129Rows, ends="close"),
-    # NOT REACHABLE by this method: FWD:74 <64, 3, 4, 129>, the 129-bin full kernel, serves batches below 8192 rows and R(64) = 32 CUs = 8192
-    C("fwd257", "fwd", 257, 64, 4, FWD + ":80 <64, 5, 4, 257>, below the 40960-row threshold", hi=kHalf257Rows - 1),
-    C("fwd257_half", "fwd", 257, 32, 8, FWD + ":79 dispatch_forward_half<9, 8, 257>", lo=kHalf257Rows, ends="close"),
-    C("fwd513", "fwd", 513, 64, 4, FWD + ":81 <64, 9, 4, 513>"),
+    C("fwd512", "fwd", 512, 64, 4, FWD + ": dispatch_forward_full_pow2 (sot_full_fwd.hpp), dispatch_forward_full_g<64, 8, 4>"),
+    C("fwd1024", "fwd", 1024, 128, 2, FWD + ": dispatch_forward_full_pow2 (sot_full_fwd.hpp), <128, 8, 2>"),
+    C("fwd2048", "fwd", 2048, 256, 1, FWD + ": dispatch_forward_full_pow2 (sot_full_fwd.hpp), <256, 8, 1>"),
+    C("fwd4096", "fwd", 4096, 512, 1, FWD + ": dispatch_forward_full_pow2 (sot_full_fwd.hpp), <512, 8, 1>"),
+    C("fwd8192", "fwd", 8192, 1024, 1, FWD + ": dispatch_forward_full, <1024, 8, 1>"),
+    C("fwd129_half", "fwd", 129, 32, 8, FWD + ": dispatch_forward_full, dispatch_forward_half<5, 8, 129> (HalfRowGeo, sot_full_fwd.hpp)", lo=kHalf129Rows, ends="close"),
+    # NOT REACHABLE by this method: FWD: dispatch_forward_full, <64, 3, 4, 129>, the 129-bin full kernel, serves batches below 8192 rows and R(64) = 32 CUs = 8192
+    C("fwd257", "fwd", 257, 64, 4, FWD + ": dispatch_forward_full, <64, 5, 4, 257>, below the 40960-row threshold", hi=kHalf257Rows - 1),
+    C("fwd257_half", "fwd", 257, 32, 8, FWD + ": dispatch_forward_full, dispatch_forward_half<9, 8, 257>", lo=kHalf257Rows, ends="close"),
+    C("fwd513", "fwd", 513, 64, 4, FWD + ": dispatch_forward_full, <64, 9, 4, 513>"),
     # two waves per row exists only below kFwd1025OneWaveRows: the largest batch it takes, 6143 rows > R(128) = 4096: SECOND ONLY
-    C("fwd1025_two_wave", "fwd", 1025, 128, 2, FWD + ":89 <128, 9, 2, 1025>", B=kFwd1025OneWaveRows - 1, hi=kFwd1025OneWaveRows - 1, iters="second only"),
-    C("fwd1025_one_wave", "fwd", 1025, 64, 4, FWD + ":88 <64, 17, 4, 1025>", lo=kFwd1025OneWaveRows, ends="close"),
-    C("fwd2049", "fwd", 2049, 256, 1, FWD + ":75 <256, 9, 1, 2049>"),
+    C("fwd1025_two_wave", "fwd", 1025, 128, 2, FWD + ": dispatch_forward_full, <128, 9, 2, 1025>", B=kFwd1025OneWaveRows - 1, hi=kFwd1025OneWaveRows - 1, iters="second only"),
+    C("fwd1025_one_wave", "fwd", 1025, 64, 4, FWD + ": dispatch_forward_full, <64, 17, 4, 1025>", lo=kFwd1025OneWaveRows, ends="close"),
+    C("fwd2049", "fwd", 2049, 256, 1, FWD + ": dispatch_forward_full, <256, 9, 1, 2049>"),
     # ---- merge-free forward (p = 1 on one grid: sot_area_full_kernel; one mode) ----
-    C("area512", "area", 512, 64, 4, FWD + ":11 dispatch_area_full_g<64, 8, 4>"),
-    C("area1024", "area", 1024, 128, 2, FWD + ":12 <128, 8, 2>"),
-    C("area2048", "area", 2048, 256, 1, FWD + ":13 <256, 8, 1> (the plain loop: a row's loss is stored behind barrier 1 of the next row)"),
-    C("area4096", "area", 4096, 512, 1, FWD + ":14 <512, 8, 1>"),
-    C("area8192", "area", 8192, 1024, 1, FWD + ":15 <1024, 8, 1>"),
-    C("area129_half", "area", 129, 32, 8, FWD + ":17 dispatch_area_half<5, 8, 129> (every batch size)"),
-    C("area257", "area", 257, 64, 4, FWD + ":20 <64, 5, 4, 257>"),
-    C("area513", "area", 513, 64, 4, FWD + ":21 <64, 9, 4, 513>"),
-    C("area1025", "area", 1025, 64, 4, FWD + ":24 <64, 17, 4, 1025>"),
-    C("area2049", "area", 2049, 256, 1, FWD + ":18 <256, 9, 1, 2049>"),
+    C("area512", "area", 512, 64, 4, FWD + ": dispatch_area_full_pow2 (sot_full_fwd.hpp), dispatch_area_full_g<64, 8, 4>"),
+    C("area1024", "area", 1024, 128, 2, FWD + ": dispatch_area_full_pow2 (sot_full_fwd.hpp), <128, 8, 2>"),
+    C("area2048", "area", 2048, 256, 1, FWD + ": dispatch_area_full_pow2 (sot_full_fwd.hpp), <256, 8, 1> (the plain loop: a row's loss is stored behind barrier 1 of the next row)"),
+    C("area4096", "area", 4096, 512, 1, FWD + ": dispatch_area_full_pow2 (sot_full_fwd.hpp), <512, 8, 1>"),
+    C("area8192", "area", 8192, 1024, 1, FWD + ": dispatch_area_full, <1024, 8, 1>"),
+    C("area129_half", "area", 129, 32, 8, FWD + ": dispatch_area_full, dispatch_area_half<5, 8, 129> (every batch size)"),
+    C("area257", "area", 257, 64, 4, FWD + ": dispatch_area_full, <64, 5, 4, 257>"),
+    C("area513", "area", 513, 64, 4, FWD + ": dispatch_area_full, <64, 9, 4, 513>"),
+    C("area1025", "area", 1025, 64, 4, FWD + ": dispatch_area_full, <64, 17, 4, 1025>"),
+    C("area2049", "area", 2049, 256, 1, FWD + ": dispatch_area_full, <256, 9, 1, 2049>"),
     # ---- run-time lengths ----
     C("rt2000", "fwd", 2000, 256, 1, RT + ":17 <256, 8, 1, -1> (2048 geometry)"),
     C("rt1500", "fwd", 1500, 192, 1, RT + ":15 <192, 8, 1, -1> (1536 geometry)"),
@@ -104,22 +104,22 @@ CASES = [
     C("gen300x411", "fwd", 300, 64, 4, PICK + " (64, 8), n != m", m=411, flags=NS),
     # ---- per-row positions: the pre-sort kernel (launch_rowpos_sort: one wave per array, 2 B arrays; it loops too: 2 B > 3 * 32 CUs except at
     #      2048 points, where 2 B = 12294 arrays guarantee its second round and, by the launch's own cap of 16 waves per CU, the third) + RP kernels ----
-    C("rp512", "fwd", 512, 64, 4, HIP + ":506 full_rp -> dispatch_forward_full_rowpos_g<64>; " + HIP + ":384 launch_rowpos_sort", rowpos=True),
-    C("rp1024", "fwd", 1024, 128, 2, HIP + ":506 -> dispatch_forward_full_rowpos_g<128>", rowpos=True),
-    C("rp2048", "fwd", 2048, 256, 1, HIP + ":506 -> dispatch_forward_full_rowpos_g<256>", rowpos=True),
-    C("rp700_generic", "fwd", 700, 128, 2, HIP + ":514 dispatch_forward<true>, " + PICK + " (128, 12)", rowpos=True),
-    C("rp2048_stored_perm", "fwd_perm", 2048, 256, 1, HIP + ":447-459 row_perm_out, then row_perm_in", rowpos=True),
-    C("rp700_stored_perm", "fwd_perm", 700, 128, 2, HIP + ":447-459 on the generic gathering kernel", rowpos=True),
+    C("rp512", "fwd", 512, 64, 4, HIP + ": run_forward, full_rp -> dispatch_forward_full_rowpos_g<64>; " + HIP + ": launch_rowpos_sort", rowpos=True),
+    C("rp1024", "fwd", 1024, 128, 2, HIP + ": run_forward -> dispatch_forward_full_rowpos_g<128>", rowpos=True),
+    C("rp2048", "fwd", 2048, 256, 1, HIP + ": run_forward -> dispatch_forward_full_rowpos_g<256>", rowpos=True),
+    C("rp700_generic", "fwd", 700, 128, 2, HIP + ": run_forward, dispatch_forward<true>, " + PICK + " (128, 12)", rowpos=True),
+    C("rp2048_stored_perm", "fwd_perm", 2048, 256, 1, HIP + ": setup_launch, row_perm_out, then row_perm_in", rowpos=True),
+    C("rp700_stored_perm", "fwd_perm", 700, 128, 2, HIP + ": setup_launch, on the generic gathering kernel", rowpos=True),
     # ---- backward: both gradients / y only ----
-    C("bwd512", "bwd", 512, 64, 4, BWD + ":31 dispatch_backward_full_g<64, 8, 4>"),
-    C("bwd1024", "bwd", 1024, 128, 2, BWD + ":34 <128, 8, 2, 0, 1>; y only :33 the slim layout dispatch_backward_full_y<128, 8, 2, 0, true, 1>"),
-    C("bwd2048", "bwd", 2048, 256, 1, BWD + ":37 <256, 8, 1, 0, 1>; y only :36 dispatch_backward_full_y<256, 8, 2> (two rows per workgroup)"),
-    C("bwd4096", "bwd", 4096, 512, 1, BWD + ":38 <512, 8, 1>"),
-    C("bwd129", "bwd", 129, 64, 4, BWD + ":39 <64, 3, 4, 129>"),
-    C("bwd257", "bwd", 257, 64, 4, BWD + ":44 <64, 5, 4, 257>"),
-    C("bwd513", "bwd", 513, 64, 4, BWD + ":48 <64, 9, 4, 513, 1>; y only :47 slim"),
-    C("bwd1025", "bwd", 1025, 128, 2, BWD + ":53 <128, 9, 2, 1025, 1>; y only :52 slim"),
-    C("bwd2049", "bwd", 2049, 256, 1, BWD + ":42 <256, 9, 1, 2049, 1>; y only :41 slim"),
+    C("bwd512", "bwd", 512, 64, 4, BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp), dispatch_backward_full_g<64, 8, 4>"),
+    C("bwd1024", "bwd", 1024, 128, 2, BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp), <128, 8, 2, 0, 1>; y only: the slim layout dispatch_backward_full_y<128, 8, 2, 0, true, 1>"),
+    C("bwd2048", "bwd", 2048, 256, 1, BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp), <256, 8, 1, 0, 1>; y only: dispatch_backward_full_y<256, 8, 2> (two rows per workgroup)"),
+    C("bwd4096", "bwd", 4096, 512, 1, BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp), <512, 8, 1>"),
+    C("bwd129", "bwd", 129, 64, 4, BWD + ": dispatch_backward_full, <64, 3, 4, 129>"),
+    C("bwd257", "bwd", 257, 64, 4, BWD + ": dispatch_backward_full, <64, 5, 4, 257>"),
+    C("bwd513", "bwd", 513, 64, 4, BWD + ": dispatch_backward_full, <64, 9, 4, 513, 1>; y only: slim"),
+    C("bwd1025", "bwd", 1025, 128, 2, BWD + ": dispatch_backward_full, <128, 9, 2, 1025, 1>; y only: slim"),
+    C("bwd2049", "bwd", 2049, 256, 1, BWD + ": dispatch_backward_full, <256, 9, 1, 2049, 1>; y only: slim"),
     C("bwd_rt2000", "bwd", 2000, 256, 1, "csrc/sot_full_rt_bwd.hip:21 <256, 8, 1, -1>"),
     C("bwd_rt1500", "bwd", 1500, 192, 1, "csrc/sot_full_rt_bwd.hip:20 <192, 8, 1, -1>"),
     C("bwd_rt200", "bwd", 200, 64, 4, "csrc/sot_full_rt_bwd.hip:15 <64, 4, 4, -1>"),
@@ -129,15 +129,15 @@ CASES = [
     C("bwd_gen1800", "bwd", 1800, 256, 1, PICK + " (256, 8)", flags=NS),
     C("bwd_gen2100", "bwd", 2100, 1024, 1, PICK + " (1024, 8): the smallest length of the geometry in round figures (see the note below CASES)", flags=NS),
     C("bwd_gen300x411", "bwd", 300, 64, 4, PICK + " (64, 8), n != m", m=411, flags=NS),
-    C("bwd_rp512", "bwd", 512, 64, 4, HIP + ":540 full_rp -> dispatch_backward_full_rowpos_g<64>", rowpos=True),
-    C("bwd_rp2048", "bwd", 2048, 256, 1, HIP + ":540 -> dispatch_backward_full_rowpos_g<256>", rowpos=True),
-    C("bwd_rp700_generic", "bwd", 700, 128, 2, HIP + ":556 dispatch_backward<true>, " + PICK + " (128, 12)", rowpos=True),
+    C("bwd_rp512", "bwd", 512, 64, 4, HIP + ": run_backward, full_rp -> dispatch_backward_full_rowpos_g<64>", rowpos=True),
+    C("bwd_rp2048", "bwd", 2048, 256, 1, HIP + ": run_backward -> dispatch_backward_full_rowpos_g<256>", rowpos=True),
+    C("bwd_rp700_generic", "bwd", 700, 128, 2, HIP + ": run_backward, dispatch_backward<true>, " + PICK + " (128, 12)", rowpos=True),
     # ---- training form (row losses + d mean / d y from one pass) and the merge-free training form ----
-    C("train512", "train", 512, 64, 4, HIP + ":542 row losses from the y-only kernel; " + BWD + ":31"),
-    C("train2048", "train", 2048, 256, 1, HIP + ":542; " + BWD + ":36"),
-    C("train1025", "train", 1025, 128, 2, HIP + ":542; " + BWD + ":52"),
-    C("tiefree2048", "tiefree", 2048, 256, 1, HIP + ":550 area -> " + BWD + ":13 dispatch_area_train_g<256, 8, 1>"),
-    C("tiefree1025", "tiefree", 1025, 128, 2, HIP + ":550 -> " + BWD + ":18 dispatch_area_train_g<128, 9, 2, 1025>"),
+    C("train512", "train", 512, 64, 4, HIP + ": run_backward, row losses from the y-only kernel; " + BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp)"),
+    C("train2048", "train", 2048, 256, 1, HIP + ": run_backward; " + BWD + ": dispatch_backward_full_pow2 (sot_full_bwd.hpp)"),
+    C("train1025", "train", 1025, 128, 2, HIP + ": run_backward; " + BWD + ": dispatch_backward_full"),
+    C("tiefree2048", "tiefree", 2048, 256, 1, HIP + ": run_backward, area -> " + BWD + ": dispatch_area_train, dispatch_area_train_g<256, 8, 1>"),
+    C("tiefree1025", "tiefree", 1025, 128, 2, HIP + ": run_backward -> " + BWD + ": dispatch_area_train, dispatch_area_train_g<128, 9, 2, 1025>"),
     # ---- position gradients: one shared and one per-row case per generic geometry whose gradient layout fits the LDS ((1024, 16) does not) ----
     C("posgrad300", "posgrad", 300, 64, 4, "csrc/sot_posgrad.hip:202 setup_launch, " + PICK + " (64, 8)"),
     #      (the longer side picks the geometry; the other side is short because chance ties between the two sides' levels grow with n m / 2^24)
@@ -149,7 +149,7 @@ CASES = [
     C("posgrad_rp1600x100", "posgrad", 1600, 256, 1, PICK + " (256, 8), per-row positions", m=100, rowpos=True),
     C("posgrad_rp2100x90", "posgrad", 2100, 1024, 1, PICK + " (1024, 8), per-row positions", m=90, rowpos=True),
     # ---- quantile tensors and their gradients: n + m <= 600 keeps the [B, n + m] outputs small, which leaves the geometries (64, 8) and (128, 12) ----
-    C("quant300", "quant", 300, 64, 4, HIP + ":667 run_forward(quant), " + PICK + " (64, 8)"),
+    C("quant300", "quant", 300, 64, 4, HIP + ": sot_w1d_quantiles, run_forward(quant), " + PICK + " (64, 8)"),
     C("quant520x80", "quant", 520, 128, 2, PICK + " (128, 12)", m=80),
     C("quant_rp300", "quant", 300, 64, 4, PICK + " (64, 8), per-row positions", rowpos=True),
     C("quant_rp520x80", "quant", 520, 128, 2, PICK + " (128, 12), per-row positions", m=80, rowpos=True),
@@ -161,12 +161,12 @@ CASES = [
     C("csr64", "csr", 64, 64, 4, "csrc/sot_csr.hip:39 " + PICK + " (64, 8) of (max_n, max_m)"),
     C("csr500", "csr", 500, 64, 4, "csrc/sot_csr.hip:39 " + PICK + " (64, 8)"),
     # ---- segmented sort: one wave per row (sot_segmented_sort: n <= 2048), i.e. R = 32 CUs rows ----
-    C("sort100", "sort", 100, 64, 4, HIP + ":770 launch_segmented_sort_wave<2>"),
-    C("sort512", "sort", 512, 64, 4, HIP + ":771 launch_segmented_sort_wave<8>"),
-    C("sort2048", "sort", 2048, 64, 4, HIP + ":773 launch_segmented_sort_wave<32>"),
+    C("sort100", "sort", 100, 64, 4, HIP + ": sot_segmented_sort, launch_segmented_sort_wave<2>"),
+    C("sort512", "sort", 512, 64, 4, HIP + ": sot_segmented_sort, launch_segmented_sort_wave<8>"),
+    C("sort2048", "sort", 2048, 64, 4, HIP + ": sot_segmented_sort, launch_segmented_sort_wave<32>"),
     # ---- the batch mean in the row kernel's last workgroup ----
-    C("fused2048", "fused", 2048, 256, 1, HIP + ":496 mean_tail; " + FWD + ":13 / :68"),
-    C("fused513", "fused", 513, 64, 4, HIP + ":496 mean_tail; " + FWD + ":21 / :81"),
+    C("fused2048", "fused", 2048, 256, 1, HIP + ": run_forward, mean_tail; " + FWD + ": dispatch_area_full_pow2 (sot_full_fwd.hpp) / dispatch_forward_full_pow2 (sot_full_fwd.hpp)"),
+    C("fused513", "fused", 513, 64, 4, HIP + ": run_forward, mean_tail; " + FWD + ": dispatch_area_full / dispatch_forward_full"),
 ]
 # Lengths the issue leaves open are the smallest that reach the kernel or geometry (just past the previous geometry's capacity, no multiple of
 # the tile).  The generic backward on (1024, 8) first ran at 5000 points as the forward does: paper mode's d / d y came out at 1.065e-5 of the
