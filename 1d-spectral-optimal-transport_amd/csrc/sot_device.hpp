@@ -149,6 +149,17 @@ __device__ __forceinline__ float div_by_row_constant(float x, float S, float r, 
     risk = min(risk, __float_as_uint(x) - 1u);  // x == 0 (exact either way) wraps to UINT_MAX
     return q1;
 }
+// Two adjacent elements of one row at once: they share S and r, and each half is the scalar sequence above, operation for operation
+// (v_pk_mul_f32, v_pk_fma_f32 with neg on the product, v_pk_fma_f32: 3 VALU per pair instead of 6), so the quotients are the same bits.
+// The operand screen is the caller's (full_build_cdfs, PLAIN).
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 div_by_row_constant(f32x2 x, float S, float r)
+{
+    const f32x2 Sv = {S, S}, rv = {r, r};
+    const f32x2 q0 = x * rv;
+    const f32x2 e = __builtin_elementwise_fma(-q0, Sv, x);
+    return __builtin_elementwise_fma(e, rv, q0);
+}
 
 // ---------------------------------------------------------------------------------------------
 // Wave-level scans / reductions.  Forward scans use DPP (row_shr 1/2/4/8, row_bcast 15/31,

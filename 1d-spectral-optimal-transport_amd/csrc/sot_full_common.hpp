@@ -624,10 +624,30 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
     {
         float qx[CPT], qy[CPT];
         uint32_t risk = 0xFFFFFFFFu;
+        if constexpr (PLAIN && CPT % 2 == 0) {
+            // the owned elements sit in consecutive registers (two 16-byte LDS reads per array): the division on pairs, written out so
+            // that it does not hang on the vectoriser.  The operand screen costs one v_min3_u32 per two elements instead of a subtraction
+            // per element on top: `low` is the smallest operand pattern, zeros included, and no operand in [1, 2^-78] can hide above it,
+            // so the exact test (which tells a zero from a tiny weight) runs only in waves that hold a zero or a tiny weight
+            static_assert(!(SQ && !PRESQ), "the plain loop stages squares: the operands are wx / wy as read");
+            uint32_t low = 0xFFFFFFFFu;
+#pragma unroll
+            for (int k = 0; k < CPT; k += 2) {
+                const f32x2 q = div_by_row_constant(f32x2{wx[k], wx[k + 1]}, Sxh, rSx), r = div_by_row_constant(f32x2{wy[k], wy[k + 1]}, Syh, rSy);
+                qx[k] = q.x; qx[k + 1] = q.y; qy[k] = r.x; qy[k + 1] = r.y;
+            }
+#pragma unroll
+            for (int k = 0; k < CPT; ++k) low = min(min(low, __float_as_uint(wx[k])), __float_as_uint(wy[k]));
+            if (__builtin_amdgcn_ballot_w64(low <= kFastDivMinBits) != 0ull) {   // risk < kFastDivMinBits implies this
+#pragma unroll
+                for (int k = 0; k < CPT; ++k) risk = min(risk, min(__float_as_uint(wx[k]) - 1u, __float_as_uint(wy[k]) - 1u));
+            }
+        } else {
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
             qx[k] = div_by_row_constant((SQ && !PRESQ) ? wx[k] * wx[k] : wx[k], Sxh, rSx, risk);
             qy[k] = div_by_row_constant((SQ && !PRESQ) ? wy[k] * wy[k] : wy[k], Syh, rSy, risk);
+        }
         }
         const bool slow = (risk < kFastDivMinBits) || !(Sxh <= 0x1p40f) || !(Syh <= 0x1p40f);
         if (__builtin_amdgcn_ballot_w64(slow) != 0ull) {  // rare, wave-uniform (see build_cdfs)
@@ -661,10 +681,21 @@ __device__ __forceinline__ void full_build_cdfs(const FwdArgs& a, const FullCtx&
 #pragma unroll
         for (int w = 0; w < NW - 1; ++w) { tx[w] = wtot[w]; ty[w] = wtot[NW + w]; }
         double ox = 0.0, oy = 0.0;
+        if constexpr (PLAIN) {
+            // the plain loop: the same sums under an early exit on the wave's index -- as compiled, wave 0 branches around the LDS reads and the
+            // adds, waves 1 ... 3 pick their sum with 8 v_cndmask instead of 12.  (A switch over the wave's index, no select at all, measured
+            // no better: profiles/area_valu_diet.txt)
+#pragma unroll
+            for (int w = 0; w < NW - 1; ++w) {
+                if (w >= wv) break;
+                ox += tx[w]; oy += ty[w];
+            }
+        } else {
 #pragma unroll
         for (int w = 0; w < NW - 1; ++w) {
             const double sx = ox + tx[w], sy = oy + ty[w];
             ox = (w < wv) ? sx : ox; oy = (w < wv) ? sy : oy;
+        }
         }
         exx += ox; exy += oy;
     }

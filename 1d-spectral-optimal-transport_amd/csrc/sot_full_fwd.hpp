@@ -278,8 +278,13 @@ __device__ __forceinline__ void area_rows_plain(const FwdArgs& a, const FullCtx&
             nullptr, nullptr, store_pending);
         SOT_PH(sacc, 9);   // wave totals, CDF values, next row's loads issued
         float acc = 0.0f;
+        static_assert(CPT % 2 == 0, "kAreaPlainLoop: 8 elements per thread");
 #pragma unroll
-        for (int k = 0; k < CPT; ++k) acc = fmaf(fabsf(cu[k] - cv[k]), dx[k], acc);
+        for (int k = 0; k < CPT; k += 2) {   // the differences on pairs (v_pk_add_f32 with neg); the sum stays one chain in element order
+            const f32x2 d = f32x2{cu[k], cu[k + 1]} - f32x2{cv[k], cv[k + 1]};
+            acc = fmaf(fabsf(d.x), dx[k], acc);
+            acc = fmaf(fabsf(d.y), dx[k + 1], acc);
+        }
         acc = wave_sum(acc);
         if (NW == 1) {
             if (lane == 0 && valid) row_loss[row] = acc;

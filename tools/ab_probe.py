@@ -36,5 +36,7 @@ for rep in range(3):
     res.append(round(a.elapsed_time(b) * 5, 1))
 print(res)
 """
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
-        print(f"{name:14s}", r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-300:])
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+        print(f"{name:14s}", r.stdout.strip().splitlines()[-1] if r.stdout.strip() else r.stderr[-300:], flush=True)
+        if r.returncode != 0:   # nothing more is started on a device that a variant may have faulted
+            sys.exit(f"{name}: exit status {r.returncode}; stopped")
