@@ -30,6 +30,7 @@ OBJECTS = (
     ("quantgrad", "sot_quantgrad.hip"),                  # gradient of the return_quantiles tensors
     ("mixed", "sot_mixed.hip"),                          # mixed supports: a shared grid against per-row positions
     ("stft", "sot_stft.hip"),                            # the STFT-magnitude producer
+    ("spec_distance", "sot_spec_distance.hip"),          # the spectral distance of MSSLoss over its magnitudes
     ("osc", "sot_osc.hip"),                              # the oscillator bank
     ("mss", "sot_mss.hip"),                              # MSSLoss with its gradient in two launches
     ("fir", "sot_fir.hip"),                              # time-invariant FIR filter (frequency_filter / the synthesiser's roll-off)

@@ -88,7 +88,7 @@ struct MetAcc { int mask; float f[kMaxGroups]; double d[kMaxGroups]; };
 
 __device__ __forceinline__ float safe_logf(float x, float eps) { return logf(x <= eps ? eps : x); }
 
-// range test of a frame's windowed samples (csrc/sot_stft.hip: frame_is_plain): then re^2 + im^2 of its bins neither overflows nor loses the bins that matter
+// range test of a frame's windowed samples (csrc/sot_stft_common.hpp: frame_is_plain): then re^2 + im^2 of its bins neither overflows nor loses the bins that matter
 __device__ __forceinline__ bool frame_is_plain(float amax) { return (amax > 1e-9f && amax < 1e15f) || amax == 0.0f; }
 
 // the maximum over the L consecutive lanes that hold one frame (L a power of two; L = 64: the wave)
@@ -199,11 +199,11 @@ __device__ __forceinline__ void window_frames(v2f (&rt)[16], v2f (&rv)[16], cons
 
 // The bin pairs of the lane: q < 8: k = L q + l (all lanes), q = 8: k = m / 2 (lane l = 0 of each frame).  With the packed transform Z,
 // e = Z_k + conj Z_(m-k), o = Z_k - conj Z_(m-k) and the table entry w' = -i W_n^k / 2:   X_k = e / 2 + w' o,   conj X_(m-k) = e / 2 - w' o
-// (csrc/sot_stft.hip: unpack_pair, regrouped: 8 packed operations per pair).
+// (csrc/sot_stft_common.hpp: unpack_pair, regrouped: 8 packed operations per pair).
 // Pass 1 (target): |T| of both bins into tm[].  Pass 2 (estimate): |V|, the distance terms, and -- GRAD -- the Hermitian packing of the
 // gradient w.r.t. the spectrum written over Z in the buffer (the two slots of a pair are read and written by the same lane only):
 //   Zin_k = g_k X_k / |X_k| (torch: sgn(0) = 0),  H_k = Zin_k / 2 (0 < k < m), H_0 = Re Zin_0, H_m = Re Zin_m,
-//   s = H_k + conj H_(m-k), P = i conj(W) (H_k - conj H_(m-k)):   G_k = s + P,   G_(m-k) = conj(s - P)     (csrc/sot_stft.hip, backward).
+//   s = H_k + conj H_(m-k), P = i conj(W) (H_k - conj H_(m-k)):   G_k = s + P,   G_(m-k) = conj(s - P)     (csrc/sot_stft_slot.hpp: backward_partial_body).
 // KIND 0: the paper's distance (L1 on the magnitudes only: mag_weight |t - v|, float32 partial sums per lane); KIND 1: every combination
 // (L1 / L2, magnitudes and / or their safe_log; float64 partial sums).  PLAIN: the frame passed the range test: |x| = v_sqrt(re^2 + im^2),
 // 1 / |x| = v_rsq; otherwise hypotf and an IEEE division.  KIND 2: the metric mode (`a` is a MetArgs; the sums go to `mc`, see metric_bin).

@@ -2,7 +2,7 @@
 // frames of m = 2^M points each (n_fft = 2 m = 64 ... 2048): radix-4 / radix-2 stages on the position bits a lane holds in its register index,
 // one or two exchanges through the wave's own LDS buffer (1088 points) with padded, conflict-free, additive address maps, and the transposed
 // network for the inverse.  The index algebra is modelled lane by lane in tests/wave_fft_model.py and checked against numpy's FFT
-// (tests/test_wave_fft_model.py).  Used by csrc/sot_mss.hip (MSSLoss in two launches) and csrc/sot_stft.hip (n_fft 2048 producer kernels).
+// (tests/test_wave_fft_model.py).  Used by csrc/sot_mss.hip (MSSLoss in two launches) and csrc/sot_stft_wfft.hpp (n_fft 2048 producer kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,7 +23,7 @@ __device__ __forceinline__ void wave_sync()
 }
 
 // complex products on the packed-fp32 unit: one v_pk_mul_f32 + one v_pk_fma_f32 (operand halves picked by op_sel, signs by neg_*).
-// (csrc/sot_stft.hip keeps the three-rounding form for the SOT chain's knife edge; nothing here has one, and the fused form is the more accurate.)
+// (csrc/sot_stft_common.hpp keeps the three-rounding form for the SOT chain's knife edge; nothing here has one, and the fused form is the more accurate.)
 __device__ __forceinline__ v2f cmul(v2f a, v2f b)
 {
     v2f t, r;

@@ -1,7 +1,7 @@
 """Producers of the hot path's inputs for BASELINE config 5 (the training-step slice): a harmonic batch
 generator and the magnitude STFT that `trainer.py:199-200` applies before the loss.
 
-The magnitude STFT runs hand-written HIP kernels on the GPU (`csrc/sot_stft.hip` behind
+The magnitude STFT runs hand-written HIP kernels on the GPU (`csrc/sot_stft.hip` and its `csrc/sot_stft_*.hpp` kernel families behind
 `sot_stft_mag_forward` / `sot_stft_mag_backward`: in-LDS FFT per frame, closed-form backward with an in-LDS
 overlap-add per clip); `stft_magnitude_torch` is the same transform on torch ops (torch.stft -> rocFFT / pocketfft),
 kept for CPU tensors, for transform sizes the kernels do not cover and as a cross-check.  The harmonic generator is

@@ -354,9 +354,9 @@ def test_column_sum(far):
 # ---- the signal objects -------------------------------------------------------------------------------------------------------------------
 STFT = mc.STFT
 STFT_FAR = {   # name: (n_fft, hop, samples, forward dispatch, backward dispatch) for three clips
-    "slot512": (512, 128, 3001, STFT + ":1351 stft_mag_forward_kernel<8>", STFT + ":1525 partial_kernel<8> + overlap-add / :1524 spec_kernel<8>"),
-    "persistent2048": (2048, 512, 5000, STFT + ":1350 launch_forward_persistent<10>: 30 frames < 512", STFT + ":1525 partial_kernel<10> / :1524 spec_kernel<10>"),
-    "wavew2048": (2048, 256, 256 * 172 - 17, STFT + ":1404 launch_forward_wavew: 512 <= 516 frames < 3072", STFT + ":1525 / :1524 (258 groups < 1024: not wave2)"),
+    "slot512": (512, 128, 3001, STFT + " pick_forward_route -> slot: stft_mag_forward_kernel<8>", STFT + " pick_backward_route -> recomputing slot: partial_kernel<8> + overlap-add / slot from spectrum: spec_kernel<8>"),
+    "persistent2048": (2048, 512, 5000, STFT + " pick_forward_route: 30 frames < 512 -> persistent slot", STFT + " pick_backward_route -> recomputing slot: partial_kernel<10> / slot from spectrum: spec_kernel<10>"),
+    "wavew2048": (2048, 256, 256 * 172 - 17, STFT + " pick_forward_route: 512 <= 516 frames < 3072 -> wavew", STFT + " pick_backward_route -> the slot routes (258 groups < 1024: not wave2)"),
 }
 
 
@@ -613,10 +613,10 @@ def test_dense_segmented_sort_2048():
 
 
 def test_dense_stft_wave2_forward_and_backward():
-    """sot_stft_mag_forward, n_fft 2048 / hop 256 on stft_mag_forward_wave2_kernel (csrc/sot_stft.hip:1362), mag only: 17 frames per clip and the
+    """sot_stft_mag_forward, n_fft 2048 / hop 256 on stft_mag_forward_wave2_kernel (csrc/sot_stft.hip pick_forward_route -> wave2), mag only: 17 frames per clip and the
     smallest batch for which mag [clips, 17, 1025] has more than 2^31 elements; then the backward that reads a grad_mag of that size, from the
-    stored spectrum on stft_mag_backward_spec_wave2_kernel (:1386: 17 > 16 frames, so not the clip kernel) with the overlap-add behind it.
-    The last min(CUs, 64) clips alone run other kernels (:1404 wavew forward, below 3072 frames; :1524 the slot backward, below 1024 groups):
+    stored spectrum on stft_mag_backward_spec_wave2_kernel (pick_backward_route -> wave2 from spectrum: 17 > 16 frames, so not the clip kernel) with the overlap-add behind it.
+    The last min(CUs, 64) clips alone run other kernels (pick_forward_route -> wavew, below 3072 frames; pick_backward_route -> slot from spectrum, below 1024 groups):
     1e-6 of the peak forward, 2e-5 of the gradient's peak backward, the bounds of test_one_wave_per_frame_kernels_of_large_batches, which
     also supplies the bounds of the sample: torch.stft -- here in float64 -- within 2e-6 of the peak, the recomputing slot kernel on batches
     of 8 clips within 2e-5 of the gradient's peak."""

@@ -65,8 +65,8 @@ ALL, DENSE = ("A", "O", "S"), ("A", "O")
 
 # The `close` column: layout -> the dispatch line that sends this layout to ANOTHER kernel than layout A's, so that condition 6 is a tolerance there.
 # Every layout a line does not name here is held to A bit for bit.
-WAVE2_SCRATCH = ("csrc/sot_stft.hip:1387 launch_backward_spec_wave2 needs the scratch rows on 8-byte boundaries: with the workspace 4 bytes off the grid "
-                 ":1524 stft_mag_backward_spec_kernel<10>, the slot kernel, serves the call (another FFT, another association)")
+WAVE2_SCRATCH = ("csrc/sot_stft.hip pick_backward_route: wave2 from spectrum needs the scratch rows on 8-byte boundaries: with the workspace 4 bytes off the grid "
+                 "stft_mag_backward_spec_kernel<10>, the slot kernel (slot from spectrum), serves the call (another FFT, another association)")
 TIE_FREE_2048 = ("csrc/sot_hip.hip: run_backward, `full` needs backward_full_supports(2048, aligned16) and `area` needs `full`: with rows 4 bytes off the grid "
                  ":555 dispatch_backward_full_rt, the merge walk, serves the call -- SOT_FLAG_TIE_FREE_GRADIENT is a permission (include/sot_hip.h)")
 NOT_BITWISE = {"tiefree2048": {"O": TIE_FREE_2048, "S": TIE_FREE_2048}}     # for the lines taken over from tests/test_row_loop_gpu.py
@@ -120,11 +120,11 @@ CASES += [
 # ---- the side kernels: the smallest shape that satisfies each dispatch predicate of csrc/sot_stft.hip ----
 STFT = "csrc/sot_stft.hip"
 STFT_GEO = {   # name: (n_fft, hop, batch, samples, the predicate)
-    "slot64": (64, 16, 3, 1000, STFT + ":1351 stft_mag_forward_kernel<5>, the clip ends inside a frame"),
-    "slot512": (512, 128, 2, 3001, STFT + ":1351 stft_mag_forward_kernel<8>, the clip ends inside a frame"),
-    "persistent2048": (2048, 512, 2, 5000, STFT + ":1350 launch_forward_persistent<10>: fewer than 512 frames"),
-    "wavew2048": (2048, 256, 2, 256 * 300 - 17, STFT + ":1404 launch_forward_wavew: 512 <= 600 frames < 3072"),
-    "wave2_2048": (2048, 256, 2, 256 * 1600 - 5, STFT + ":1362 launch_forward_wave2: 3200 frames >= 3072"),
+    "slot64": (64, 16, 3, 1000, STFT + " pick_forward_route -> slot: stft_mag_forward_kernel<5>, the clip ends inside a frame"),
+    "slot512": (512, 128, 2, 3001, STFT + " pick_forward_route -> slot: stft_mag_forward_kernel<8>, the clip ends inside a frame"),
+    "persistent2048": (2048, 512, 2, 5000, STFT + " pick_forward_route: fewer than 512 frames -> persistent slot"),
+    "wavew2048": (2048, 256, 2, 256 * 300 - 17, STFT + " pick_forward_route: 512 <= 600 frames < 3072 -> wavew"),
+    "wave2_2048": (2048, 256, 2, 256 * 1600 - 5, STFT + " pick_forward_route: 3200 frames >= 3072 -> wave2"),
 }
 for geo, (n_fft, hop, batch, samples, cite) in STFT_GEO.items():
     CASES += [
@@ -134,12 +134,12 @@ for geo, (n_fft, hop, batch, samples, cite) in STFT_GEO.items():
         C(f"stft_pair_spec_{geo}", "sot_stft_mag_forward_pair_spec", "stft_fwd", cite=cite, geo=geo, pair=True, spec=True),
     ]
 STFT_BWD_GEO = {   # name: (n_fft, hop, batch, samples, from the stored spectrum?, the predicate)
-    "audio512": (512, 128, 2, 3001, False, STFT + ":1525 stft_mag_backward_partial_kernel<8> + stft_overlap_add_kernel"),
-    "audio2048": (2048, 512, 2, 5000, False, STFT + ":1525 stft_mag_backward_partial_kernel<10>"),
-    "spec_slot512": (512, 128, 2, 3001, True, STFT + ":1524 stft_mag_backward_spec_kernel<8>"),
-    "spec_clip2048": (2048, 512, 65, 512 * 6 - 7, True, STFT + ":1376 launch_backward_spec_clip: 65 >= 64 clips of 6 <= 16 frames, even hop"),
-    "spec_wave2_2048": (2048, 256, 2, 256 * 1600 - 5, True, STFT + ":1386 launch_backward_spec_wave2: 1600 >= 1024 groups, hop 256, 8-byte scratch rows"),
-    "spec_wave2_hop512": (2048, 512, 2, 512 * 1100 - 5, True, STFT + ":1396 launch_backward_spec_wave2, hop 512: 1100 groups"),
+    "audio512": (512, 128, 2, 3001, False, STFT + " pick_backward_route -> recomputing slot: stft_mag_backward_partial_kernel<8> + stft_overlap_add_kernel"),
+    "audio2048": (2048, 512, 2, 5000, False, STFT + " pick_backward_route -> recomputing slot: stft_mag_backward_partial_kernel<10>"),
+    "spec_slot512": (512, 128, 2, 3001, True, STFT + " pick_backward_route -> slot from spectrum: stft_mag_backward_spec_kernel<8>"),
+    "spec_clip2048": (2048, 512, 65, 512 * 6 - 7, True, STFT + " pick_backward_route: 65 >= 64 clips of 6 <= 16 frames, even hop -> clip"),
+    "spec_wave2_2048": (2048, 256, 2, 256 * 1600 - 5, True, STFT + " pick_backward_route: 1600 >= 1024 groups, hop 256, 8-byte scratch rows -> wave2 from spectrum"),
+    "spec_wave2_hop512": (2048, 512, 2, 512 * 1100 - 5, True, STFT + " pick_backward_route -> wave2 from spectrum, launch_backward_wave2<4> (hop 512): 1100 groups"),
 }
 for geo, (n_fft, hop, batch, samples, from_spec, cite) in STFT_BWD_GEO.items():
     entry = "sot_stft_mag_backward_spec" if from_spec else "sot_stft_mag_backward"
@@ -148,13 +148,13 @@ for geo, (n_fft, hop, batch, samples, from_spec, cite) in STFT_BWD_GEO.items():
               C(f"stft_bwd_{geo}_accumulate", entry, "stft_bwd", cite=cite, close=close, geo=geo, accumulate=1)]
 MSS, OSC, FIR = "csrc/sot_mss.hip", "csrc/sot_osc.hip", "csrc/sot_fir.hip"
 CASES += [
-    C("dist_fwd_1000", "sot_spec_distance_forward", "dist_fwd", 1000, cite=STFT + ":1548 four partial blocks", layouts=DENSE, accumulate=0, l2=0),
-    C("dist_fwd_262921_accumulate", "sot_spec_distance_forward", "dist_fwd", 262144 + 777, cite=STFT + ":1545 n_partial capped at kDistBlocks", layouts=DENSE, accumulate=1, l2=1),
-    C("dist_bwd_1000", "sot_spec_distance_backward", "dist_bwd", 1000, cite=STFT + ":1567 spec_distance_backward_kernel", layouts=DENSE, l2=0),
-    C("dist_bwd_262921", "sot_spec_distance_backward", "dist_bwd", 262144 + 777, cite=STFT + ":1567", layouts=DENSE, l2=1),
-    C("dist_rows_fwd_5x1300", "sot_spec_distance_rows_forward", "dist_rows_fwd", 1300, rows=None, cite=STFT + ":1581 one 1024-thread workgroup per row", layouts=DENSE, accumulate=0, l2=0),
-    C("dist_rows_fwd_5x1300_accumulate", "sot_spec_distance_rows_forward", "dist_rows_fwd", 1300, rows=None, cite=STFT + ":1581", layouts=DENSE, accumulate=1, l2=1),
-    C("dist_rows_bwd_5x1300", "sot_spec_distance_rows_backward", "dist_rows_bwd", 1300, rows=None, cite=STFT + ":1599 spec_distance_rows_backward_kernel", layouts=DENSE, l2=0),
+    C("dist_fwd_1000", "sot_spec_distance_forward", "dist_fwd", 1000, cite="csrc/sot_spec_distance.hip sot_spec_distance_forward: four partial blocks", layouts=DENSE, accumulate=0, l2=0),
+    C("dist_fwd_262921_accumulate", "sot_spec_distance_forward", "dist_fwd", 262144 + 777, cite="csrc/sot_spec_distance.hip sot_spec_distance_forward: n_partial capped at kDistBlocks", layouts=DENSE, accumulate=1, l2=1),
+    C("dist_bwd_1000", "sot_spec_distance_backward", "dist_bwd", 1000, cite="csrc/sot_spec_distance.hip sot_spec_distance_backward: spec_distance_backward_kernel", layouts=DENSE, l2=0),
+    C("dist_bwd_262921", "sot_spec_distance_backward", "dist_bwd", 262144 + 777, cite="csrc/sot_spec_distance.hip sot_spec_distance_backward", layouts=DENSE, l2=1),
+    C("dist_rows_fwd_5x1300", "sot_spec_distance_rows_forward", "dist_rows_fwd", 1300, rows=None, cite="csrc/sot_spec_distance.hip sot_spec_distance_rows_forward: one 1024-thread workgroup per row", layouts=DENSE, accumulate=0, l2=0),
+    C("dist_rows_fwd_5x1300_accumulate", "sot_spec_distance_rows_forward", "dist_rows_fwd", 1300, rows=None, cite="csrc/sot_spec_distance.hip sot_spec_distance_rows_forward", layouts=DENSE, accumulate=1, l2=1),
+    C("dist_rows_bwd_5x1300", "sot_spec_distance_rows_backward", "dist_rows_bwd", 1300, rows=None, cite="csrc/sot_spec_distance.hip sot_spec_distance_rows_backward: spec_distance_rows_backward_kernel", layouts=DENSE, l2=0),
     C("mss_one_chunk", "sot_mss_loss_and_grad", "mss", 3000, cite=MSS + ": one 4096-sample chunk per (scale, clip)", per_clip=0, grad=True),
     C("mss_two_chunks", "sot_mss_loss_and_grad", "mss", 5000, cite=MSS + ": a clip spanning two 4096-sample chunks", per_clip=0, grad=True),
     C("mss_two_chunks_per_clip", "sot_mss_loss_and_grad", "mss", 5000, cite=MSS + ": per_clip", per_clip=1, grad=True),

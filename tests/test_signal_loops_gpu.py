@@ -31,10 +31,10 @@ Each line of CASES asserts, in the order of tests/test_row_loop_gpu.py:
        metrics per clip  e_new <= 4 max(e_ref, e_stft) + 1e-6 |f64| (tests/test_eval_metrics_gpu.py: _accuracy).
 
 NOT REACHABLE by this method (asserted in test_what_no_batch_can_reach, which fails on a device where the arithmetic turns):
-  * stft_mag_forward_wavew_kernel serves 512 ... 3071 frames (csrc/sot_stft.hip:1404) on capped_grid(frames / 4, 3) (:1406): a round is
+  * stft_mag_forward_wavew_kernel serves 512 ... 3071 frames (csrc/sot_stft.hip pick_forward_route) on capped_grid(frames / 4, 3) (launch_forward_wavew): a round is
     3 CUs workgroups of 4 frames = 12 CUs frames = 3072 on 256 CUs, one more than the largest batch the kernel takes.  No workgroup runs
     a second frame group; below 256 CUs some would.
-  * stft_mag_forward_persistent_kernel serves fewer than 512 frames of n_fft 2048, one frame per workgroup (:1342, :1350), on the resident
+  * stft_mag_forward_persistent_kernel serves fewer than 512 frames of n_fft 2048, one frame per workgroup (pick_forward_route, launch_forward_persistent), on the resident
     grid of an occupancy query; amdgpu_waves_per_eu(6, 8) and 16.6 KB of LDS per 256-thread workgroup make that at least 6 CUs workgroups,
     so a second round needs 511 > 6 CUs: fewer than 86 CUs.  Its loop runs once per workgroup on every MI300-class part.
 """
@@ -52,14 +52,14 @@ from gpu_util import device, native
 pytestmark = pytest.mark.gpu
 
 STFT, OSC, MSS = "csrc/sot_stft.hip", "csrc/sot_osc.hip", "csrc/sot_mss.hip"
-kWave2Waves, kBwdWave2Waves, kFwdwWaves = 16, 8, 4      # csrc/sot_stft.hip:527, :775, :925
-kDistBlocks, kDistBwdBlocks, kThreads = 1024, 8192, 256   # :1286, :1565 / :1597, :31
-kGridY, kOlaGridX = 65535, 64                               # :1528
+kWave2Waves, kBwdWave2Waves, kFwdwWaves = 16, 8, 4      # csrc/sot_stft_wave2.hpp kWave2Waves, kBwdWave2Waves; csrc/sot_stft_wfft.hpp kFwdwWaves
+kDistBlocks, kDistBwdBlocks, kThreads = 1024, 8192, 256   # csrc/sot_spec_distance.hip kDistBlocks, kGradBlocks, kThreads
+kGridY, kOlaGridX = 65535, 64                               # csrc/sot_stft.hip sot_stft_mag_backward_spec: the overlap-add grid
 kMssFinishBlocks, kMetricFinishBlocks, kFinishThreads = 16384, 4096, 256      # csrc/sot_mss.hip:747, :831, :435
 
 Case = collections.namedtuple("Case", "id kernel cite unit n_fft hop samples clips route ends")
-WAVEW_ENDS = STFT + ":1404 launch_forward_wavew serves the 64-clip calls (576 frames < 3072): another FFT"
-SLOT_ENDS = STFT + ":1524 stft_mag_backward_spec_kernel<10> serves the 64-clip calls (576 groups < 1024): another FFT"
+WAVEW_ENDS = STFT + " pick_forward_route: wavew serves the 64-clip calls (576 frames < 3072): another FFT"
+SLOT_ENDS = STFT + " pick_backward_route: slot from spectrum, stft_mag_backward_spec_kernel<10>, serves the 64-clip calls (576 groups < 1024): another FFT"
 
 
 def _clips_for(units_per_wg, units_per_clip, must_not_divide=True):
@@ -73,21 +73,21 @@ def _clips_for(units_per_wg, units_per_clip, must_not_divide=True):
 
 # id, kernel, the launch line that caps its grid, the unit of work, n_fft, hop, samples, clips(CUs), route, ends ("bits" or the citation)
 CASES = [
-    Case("wave2_fwd", "stft_mag_forward_wave2_kernel", STFT + ":1364 capped_grid(frames / 16, 1)", "a workgroup's 16 frames", 2048, 512, 4096 + 77,
+    Case("wave2_fwd", "stft_mag_forward_wave2_kernel", STFT + " launch_forward_wave2: capped_grid(frames / 16, 1)", "a workgroup's 16 frames", 2048, 512, 4096 + 77,
          _clips_for(kWave2Waves, 9), "fwd", WAVEW_ENDS),
-    Case("wave2_bwd_hop256", "stft_mag_backward_spec_wave2_kernel<2>", STFT + ":1389 capped_grid(groups / 8, 1), :1395", "a workgroup's 8 groups of two frames", 2048, 256,
+    Case("wave2_bwd_hop256", "stft_mag_backward_spec_wave2_kernel<2>", STFT + " launch_backward_wave2<2>: capped_grid(groups / 8, 1)", "a workgroup's 8 groups of two frames", 2048, 256,
          4096 + 77, _clips_for(kBwdWave2Waves, 9), "bwd_spec", SLOT_ENDS),
-    Case("wave2_bwd_hop512", "stft_mag_backward_spec_wave2_kernel<4>", STFT + ":1389, :1396", "a workgroup's 8 groups of two frames", 2048, 512, 512 * 17 - 5,
+    Case("wave2_bwd_hop512", "stft_mag_backward_spec_wave2_kernel<4>", STFT + " launch_backward_wave2<4>", "a workgroup's 8 groups of two frames", 2048, 512, 512 * 17 - 5,
          _clips_for(kBwdWave2Waves, 9), "bwd_spec", SLOT_ENDS),
-    Case("clipw_bwd_4096", "stft_mag_backward_spec_clipw_kernel", STFT + ":1379 capped_grid(batch, 1)", "a clip of 16 frames", 2048, 256, 4096, lambda cus: 2 * cus + 1,
+    Case("clipw_bwd_4096", "stft_mag_backward_spec_clipw_kernel", STFT + " launch_backward_clip: capped_grid(batch, 1)", "a clip of 16 frames", 2048, 256, 4096, lambda cus: 2 * cus + 1,
          "bwd_spec", "bits"),
-    Case("clipw_bwd_4001", "stft_mag_backward_spec_clipw_kernel", STFT + ":1379", "a clip of 16 frames, the last two end-padded, odd length", 2048, 256, 4001,
+    Case("clipw_bwd_4001", "stft_mag_backward_spec_clipw_kernel", STFT + " launch_backward_clip", "a clip of 16 frames, the last two end-padded, odd length", 2048, 256, 4001,
          lambda cus: 2 * cus + 1, "bwd_spec", "bits"),
-    Case("ola_grid_y_audio", "stft_overlap_add_kernel behind stft_mag_backward_partial_kernel<5>", STFT + ":1528 gridDim.y = min(batch, 65535); :1525", "a clip", 64, 16,
+    Case("ola_grid_y_audio", "stft_overlap_add_kernel behind stft_mag_backward_partial_kernel<5>", STFT + " sot_stft_mag_backward_spec: overlap-add gridDim.y = min(batch, 65535); recomputing slot route", "a clip", 64, 16,
          100, lambda cus: kGridY + 2, "bwd_audio", "bits"),
-    Case("ola_grid_y_spec", "stft_overlap_add_kernel behind stft_mag_backward_spec_kernel<5>", STFT + ":1528; :1524", "a clip", 64, 16, 100, lambda cus: kGridY + 2,
+    Case("ola_grid_y_spec", "stft_overlap_add_kernel behind stft_mag_backward_spec_kernel<5>", STFT + " sot_stft_mag_backward_spec: overlap-add gridDim.y; slot from spectrum", "a clip", 64, 16, 100, lambda cus: kGridY + 2,
          "bwd_spec", "bits"),
-    Case("ola_grid_x", "stft_overlap_add_kernel", STFT + ":1528 gridDim.x = min(samples / 256, 64)", "256 samples of a clip", 512, 128, 2 * kOlaGridX * kThreads + 77,
+    Case("ola_grid_x", "stft_overlap_add_kernel", STFT + " sot_stft_mag_backward_spec: overlap-add gridDim.x = min(samples / 256, 64)", "256 samples of a clip", 512, 128, 2 * kOlaGridX * kThreads + 77,
          lambda cus: 3, "bwd_audio", "bits"),
 ]
 BY_ID = {c.id: c for c in CASES}
@@ -310,7 +310,7 @@ def distance64(t, v, mw, lw, l2, rows=None):
 
 @pytest.mark.parametrize("mw,lw,l2", [(0.5, 2.0, False), (0.3, 0.7, True)], ids=["l1", "l2"])
 def test_spec_distance_forward_loop(mw, lw, l2):
-    """spec_distance_partial_kernel: i += gridDim.x * 256 on kDistBlocks = 1024 workgroups (csrc/sot_stft.hip:1545): 2 * 1024 * 256 + 1 elements are two full
+    """spec_distance_partial_kernel: i += gridDim.x * 256 on kDistBlocks = 1024 workgroups (csrc/sot_spec_distance.hip sot_spec_distance_forward): 2 * 1024 * 256 + 1 elements are two full
     rounds and one element of a third.  The sum's order depends on the element index, so a rolled batch is another sum: in place of the
     roll, the call is repeated (deterministic), accumulates onto a base by one float32 addition, and meets float64 within 2e-6."""
     nat = native()
@@ -334,7 +334,7 @@ def test_spec_distance_forward_loop(mw, lw, l2):
 @pytest.mark.parametrize("per_row", [False, True], ids=["flat", "rows"])
 @pytest.mark.parametrize("mw,lw,l2", [(0.5, 2.0, False), (0.3, 0.7, True)], ids=["l1", "l2"])
 def test_spec_distance_backward_loops(mw, lw, l2, per_row):
-    """spec_distance_backward_kernel / spec_distance_rows_backward_kernel: grid stride on 8192 workgroups (csrc/sot_stft.hip:1565, :1597): 2 * 8192 * 256 + 1
+    """spec_distance_backward_kernel / spec_distance_rows_backward_kernel: grid stride on 8192 workgroups (csrc/sot_spec_distance.hip grad_grid: kGradBlocks): 2 * 8192 * 256 + 1
     elements (rows: 5 rows of 838861).  Elementwise, so a roll of the elements rolls the gradients: bit for bit; the ends alone cannot be bit-equal
     (the mean's 1 / count is another), they are covered by float64: 1e-5 of the gradient's peak."""
     nat, dev = native(), device()

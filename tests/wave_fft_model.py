@@ -279,7 +279,7 @@ def read_pairs(geo, lds):
 
 
 def unpack_pair(geo, k, zk, zm):
-    """bins k and m - k of the real frame of n = 2 m samples from the packed transform (csrc/sot_stft.hip: unpack_pair)"""
+    """bins k and m - k of the real frame of n = 2 m samples from the packed transform (csrc/sot_stft_common.hpp: unpack_pair)"""
     ze = 0.5 * (zk + np.conj(zm))
     zo = -0.5j * (zk - np.conj(zm))
     wz = np.exp(-2j * np.pi * k / (2 * geo.m)) * zo
@@ -287,7 +287,7 @@ def unpack_pair(geo, k, zk, zm):
 
 
 def pack_gradient_pair(geo, k, hk, hm):
-    """G_k, G_(m-k) of the Hermitian spectrum H (H_k for 0 < k < m already halved, H_0 and H_m real) -- csrc/sot_stft.hip: backward"""
+    """G_k, G_(m-k) of the Hermitian spectrum H (H_k for 0 < k < m already halved, H_0 and H_m real) -- csrc/sot_stft_slot.hpp: backward_partial_body"""
     w = np.exp(-2j * np.pi * k / (2 * geo.m))
     s, d = hk + np.conj(hm), hk - np.conj(hm)
     return s + 1j * np.conj(w) * d, np.conj(s) + 1j * w * np.conj(d)
