@@ -31,7 +31,7 @@ SOT_ERR_UNSUPPORTED_SIZE = -3
 SOT_ERR_NULL_POINTER = -4
 SOT_ERR_WORKSPACE = -5
 SOT_ERR_LAUNCH = -6
-ABI_VERSION = 20                  # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
+ABI_VERSION = 21                # include/sot_hip.h: SOT_ABI_VERSION (bumped with every signature change)
 COMPLETION_COUNTER_WORDS = 16    # include/sot_hip.h: SOT_COMPLETION_COUNTER_WORDS
 FIR_TILE = 1024                  # include/sot_hip.h: SOT_FIR_TILE (outputs per workgroup of the FIR kernel)
 FIR_MIN_TAPS, FIR_MAX_TAPS, FIR_MAX_SAMPLES = 3, 512, 1 << 20   # the FIR kernels' domain (include/sot_hip.h: sot_fir_same_forward)
@@ -52,6 +52,14 @@ class SotProblem(ctypes.Structure):
                 ("p", ctypes.c_float), ("flags", ctypes.c_uint32),
                 ("xperm", _vp), ("yperm", _vp), ("perm_is_identity", _vp),
                 ("row_perm_out", _vp), ("row_perm_in", _vp)]
+
+
+class SotProblemF64(ctypes.Structure):   # include/sot_hip.h: sot_problem_f64
+    _fields_ = [("x", _vp), ("y", _vp), ("xpos", _vp), ("ypos", _vp),
+                ("B", ctypes.c_int64), ("n", ctypes.c_int32), ("m", ctypes.c_int32),
+                ("x_row_stride", ctypes.c_int64), ("y_row_stride", ctypes.c_int64),
+                ("xpos_row_stride", ctypes.c_int64), ("ypos_row_stride", ctypes.c_int64),
+                ("p", ctypes.c_double), ("flags", ctypes.c_uint32)]
 
 
 EXPORTS = {
@@ -83,6 +91,7 @@ EXPORTS = {
                                     _vp, _vp, ctypes.c_size_t, _vp]),
     "sot_w1d_bf16_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SotProblem)]),
     "sot_w1d_bf16_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SotProblem), ctypes.c_int, ctypes.c_int]),
+    "sot_w1d_f64_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(SotProblemF64)]),
     "sot_w1d_quantiles": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp,
                                          ctypes.c_size_t, _vp]),
     "sot_w1d_quantiles_backward": (ctypes.c_int, [ctypes.POINTER(SotProblem), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -165,6 +174,15 @@ BF16_TRAIN_EXPORTS = {
                                                   ctypes.c_size_t, _vp]),
 }
 
+# float64 rows (ABI 21; `extern` in include/sot_hip.h for the same reason): the size predicate and the two calls of csrc/sot_f64.hip.  Their
+# guard-band cases, refusals and empty batches are in tests/test_f64_gpu.py.
+F64_EXPORTS = {
+    "sot_w1d_f64_supported": (ctypes.c_int, [ctypes.POINTER(SotProblemF64), ctypes.c_int]),
+    "sot_w1d_forward_f64": (ctypes.c_int, [ctypes.POINTER(SotProblemF64), _vp, _vp, ctypes.c_size_t, _vp]),
+    "sot_w1d_backward_f64": (ctypes.c_int, [ctypes.POINTER(SotProblemF64), _vp, ctypes.c_int64, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t,
+                                            _vp]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -191,7 +209,7 @@ def load(build_if_missing: bool = True):
         elif not os.path.exists(path):
             raise RuntimeError(f"{path} is missing")
         lib = ctypes.CDLL(path)
-        for name, (res, args) in (*EXPORTS.items(), *BF16_EXPORTS.items(), *BF16_TRAIN_EXPORTS.items()):
+        for name, (res, args) in (*EXPORTS.items(), *BF16_EXPORTS.items(), *BF16_TRAIN_EXPORTS.items(), *F64_EXPORTS.items()):
             fn = getattr(lib, name)  # AttributeError here = ABI mismatch, reported loudly
             fn.restype = res
             fn.argtypes = args
@@ -657,6 +675,79 @@ def loss_and_grad_bf16(x, y, xpos, ypos, p, flags, plan=None, fused_mean=None):
     lib = load()
     _require_bf16_rows(x, y, xpos, ypos)
     return _loss_and_grad(lib.sot_w1d_loss_and_grad_bf16, torch.bfloat16, _bf16_backward_workspace, x, y, xpos, ypos, p, flags, plan, fused_mean)
+
+
+# ---- float64 rows (ABI 21; csrc/sot_f64.hip): double weights, double positions, double row losses and gradients.  Supports arrive sorted.
+
+def make_problem_f64(x, y, xpos, ypos, p, flags) -> SotProblemF64:
+    """The sot_problem_f64 of 2-D weight rows (unit inner stride) and sorted positions, 1-D on both sides (shared) or [B, .] on both.  Only
+    shapes, strides and data pointers are read, so CPU or meta stand-ins can be described too (f64_supported)."""
+    B, n = x.shape
+    m = y.shape[1]
+    pr = SotProblemF64()
+    pr.x, pr.y, pr.xpos, pr.ypos = x.data_ptr(), y.data_ptr(), xpos.data_ptr(), ypos.data_ptr()
+    pr.B, pr.n, pr.m = B, n, m
+    pr.x_row_stride = x.stride(0) if B > 1 else n
+    pr.y_row_stride = y.stride(0) if B > 1 else m
+    pr.xpos_row_stride = 0 if xpos.ndim == 1 else (xpos.stride(0) if B > 1 else n)
+    pr.ypos_row_stride = 0 if ypos.ndim == 1 else (ypos.stride(0) if B > 1 else m)
+    pr.p, pr.flags = float(p), int(flags)
+    return pr
+
+
+def f64_supported(n, m, backward=False, p=1.0, flags=0, per_row=False) -> bool:
+    """Do the float64 calls take rows of n and m points (sot_w1d_f64_supported: host arithmetic, no device is touched)?  backward: the
+    backward's larger working set."""
+    pr = SotProblemF64()
+    pr.B, pr.n, pr.m = 1, int(n), int(m)
+    pr.x_row_stride, pr.y_row_stride = int(n), int(m)
+    pr.xpos_row_stride, pr.ypos_row_stride = (int(n), int(m)) if per_row else (0, 0)
+    pr.p, pr.flags = float(p), int(flags)
+    return bool(load().sot_w1d_f64_supported(ctypes.byref(pr), int(bool(backward))))
+
+
+def _require_f64(*tensors):
+    for t in tensors:
+        if t is not None and (not t.is_cuda or t.dtype != torch.float64):
+            raise TypeError(f"the float64 calls take float64 GPU tensors; got {t.dtype} on {t.device}")
+
+
+def _f64_workspace(pr, dev):
+    nbytes = int(load().sot_w1d_f64_workspace_bytes(ctypes.byref(pr)))
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes > 0 else None
+
+
+def forward_rows_f64(x, y, xpos, ypos, p, flags) -> torch.Tensor:
+    """row_loss[B] (float64) = W_p^p per row for float64 weights and sorted float64 positions (sot_w1d_forward_f64)."""
+    lib = load()
+    _require_f64(x, y, xpos, ypos)
+    dev = x.device
+    row_loss = torch.empty(x.shape[0], dtype=torch.float64, device=dev)
+    pr = make_problem_f64(x, y, xpos, ypos, p, flags)
+    ws = _f64_workspace(pr, dev)
+    with _on_device(dev):
+        rc = lib.sot_w1d_forward_f64(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return row_loss
+
+
+def backward_rows_f64(x, y, xpos, ypos, p, flags, grad_row, need_gx=True, need_gy=True, grad_scale=1.0):
+    """(gx, gy) in float64 (sot_w1d_backward_f64).  grad_row: float64, [B] or one broadcast element, or None (1 for every row)."""
+    lib = load()
+    _require_f64(x, y, xpos, ypos, grad_row)
+    dev = x.device
+    B, n = x.shape
+    m = y.shape[1]
+    gx = torch.empty(B, n, dtype=torch.float64, device=dev) if need_gx else None
+    gy = torch.empty(B, m, dtype=torch.float64, device=dev) if need_gy else None
+    pr = make_problem_f64(x, y, xpos, ypos, p, flags)
+    ws = _f64_workspace(pr, dev)
+    g, stride = (None, 0) if grad_row is None else _grad_row_arg(grad_row, B)
+    with _on_device(dev):
+        rc = lib.sot_w1d_backward_f64(ctypes.byref(pr), _ptr(g), stride, float(grad_scale), _ptr(gx), _ptr(gy), _ptr(ws),
+                                      ws.numel() if ws is not None else 0, stream_ptr(dev))
+    check(rc, p)
+    return gx, gy
 
 
 def prepared_loss_call(x, y, xpos, ypos, p, flags, plan, row_out, mean_out, sum_out=None, stream=None):

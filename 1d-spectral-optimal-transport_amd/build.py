@@ -24,7 +24,8 @@ OBJECTS = (
     ("bwd_rowpos", "sot_bwd_rowpos.hip"),                #   ... per-row positions
     ("bf16", "sot_bf16.hip"),                            # bfloat16 rows: conversion kernels, full-row forward kernels with 16-bit loads, typed entry points
     ("bf16_bwd", "sot_bf16_bwd.hip"),                    #   ... full-row backward kernels with 16-bit loads and 16-bit gradient stores, typed entry points
-    ("core", "sot_hip.hip"),                             # small kernels, sorts, launch setup and routing, the C ABI
+    ("f64", "sot_f64.hip"),                              # float64 rows: one generic forward / backward kernel family in double, typed entry points
+    ("core", "sot_hip.hip"),                          # small kernels, sorts, launch setup and routing, the C ABI
     ("csr", "sot_csr.hip"),                              # CSR (ragged) forward
     ("posgrad", "sot_posgrad.hip"),                      # position gradient, column sum
     ("quantgrad", "sot_quantgrad.hip"),                  # gradient of the return_quantiles tensors

@@ -11,8 +11,9 @@ All arithmetic on float32 HIP-device tensors runs in the hand-written HIP librar
 include/sot_hip.h); this file only reshapes, marshals pointers and wires autograd.  bfloat16 weights on the device (autocast) are
 the float32 call on the exactly widened rows: the typed forward where no gradient is asked for; where one is, the typed backward and
 training form on the rows that have 16-bit backward kernels (_typed_training_applies), a widening kernel in front of the float32 path
--- and a narrowing one behind its gradient -- elsewhere (_hip_domain).  Tensors outside the library's domain
--- CPU tensors, float64 -- take the reference's own route, torch ops (_torch_path.py), because the reference is device- and
+-- and a narrowing one behind its gradient -- elsewhere (_hip_domain).  float64 weights on float64 positions run the float64 kernels
+(csrc/sot_f64.hip) where _f64_route_applies holds.  Tensors outside the library's domain
+-- CPU tensors, float64 outside that gate -- take the reference's own route, torch ops (_torch_path.py), because the reference is device- and
 dtype-agnostic (losses.py:129-211) and `accelerator: cpu` has to keep working.
 """
 from __future__ import annotations
@@ -245,6 +246,127 @@ class _RowLossBF16(torch.autograd.Function):
         gx, gy = nat.backward_rows_bf16(x, y, xpos, ypos, ctx.p, ctx.flags, grad_rows.float(), need_gx=ctx.needs_input_grad[0],
                                         need_gy=ctx.needs_input_grad[1], plan=ctx.plan)
         return gx, gy, None, None, None, None, None
+
+
+class _RowLossF64(torch.autograd.Function):
+    """rows[B] = W_p^p per pair in float64 (sot_w1d_forward_f64) on sorted supports that ask for no gradient; backward: the closed form in
+    double (sot_w1d_backward_f64), only the gradients asked for."""
+
+    @staticmethod
+    def forward(ctx, x, y, xpos, ypos, p, flags):
+        rows = nat.forward_rows_f64(x, y, xpos, ypos, p, flags)
+        ctx.save_for_backward(x, y, xpos, ypos)
+        ctx.p, ctx.flags = p, flags
+        return rows
+
+    @staticmethod
+    def backward(ctx, grad_rows):
+        x, y, xpos, ypos = ctx.saved_tensors
+        gx, gy = nat.backward_rows_f64(x, y, xpos, ypos, ctx.p, ctx.flags, grad_rows.double(), need_gx=ctx.needs_input_grad[0],
+                                       need_gy=ctx.needs_input_grad[1])
+        return gx, gy, None, None, None, None
+
+
+F64_ROUTE = True   # module switch (tools/bench_f64.py times both routes): False = float64 GPU tensors run the torch-op composition as before
+_F64_FLAGS = nat.FLAG_SQUARE | nat.FLAG_DONT_NORMALIZE | nat.FLAG_LIMIT_Q | nat.FLAG_PRENORMALIZED   # what the float64 kernels honour
+
+
+def _is_hip_tensor(t) -> bool:
+    return t.is_cuda
+
+
+def _f64_route_applies(x, y, xpos, ypos, return_quantiles=False) -> bool:
+    """Does a call take the float64 kernels (sot_w1d_forward_f64 / sot_w1d_backward_f64)?  It does when all four tensors are float64 on ONE
+    HIP device, neither position tensor asks for a gradient, the call is not return_quantiles, not the mixed-supports case (a shared grid
+    against per-row positions) and not being traced, and the rows fit the kernels (nat.f64_supported: one pair's working set in one CU's
+    LDS; the backward's when a gradient is asked for).  Everything else -- float32 positions, position gradients, quantiles, mixed supports,
+    long rows, compiled calls -- keeps the torch-op composition and its one-time warning.  A function of dtypes, devices, shapes, strides,
+    requires_grad and the grad mode: no device is touched."""
+    if not F64_ROUTE or _compiling() or return_quantiles:
+        return False
+    ts = (x, y, xpos, ypos)
+    if any(t is None or t.dtype is not torch.float64 or not _is_hip_tensor(t) or t.device != x.device for t in ts):
+        return False
+    grad_on = torch.is_grad_enabled()
+    if grad_on and (xpos.requires_grad or ypos.requires_grad):
+        return False
+    if not (2 <= x.ndim <= 3 and x.ndim == y.ndim) or x.shape[:-1] != y.shape[:-1] or xpos.ndim > 3 or ypos.ndim > 3:
+        return False
+    n, m = x.shape[-1], y.shape[-1]
+    if n < 1 or m < 1 or xpos.shape[-1] != n or ypos.shape[-1] != m:
+        return False    # (the general path says what is wrong with such a call)
+    shared = _is_shared_row(xpos)
+    if shared != _is_shared_row(ypos):
+        return False
+    if not shared:
+        rows = x.numel() // n
+        if xpos.numel() != rows * n or ypos.numel() != rows * m:
+            return False
+    return nat.f64_supported(n, m, backward=grad_on and (x.requires_grad or y.requires_grad), per_row=not shared)
+
+
+class _SortedGridCache:
+    """Stable sorts of shared float64 position rows, keyed by tensor identity + version like _PlanCache: (sorted row, permutation), with the
+    permutation None when the row was sorted already -- decided once per tensor version with one host synchronisation, outside stream
+    capture (inside a capture of a grid not seen before, the sort and the gather are enqueued and nothing is remembered)."""
+
+    def __init__(self, capacity=8):
+        self.capacity = capacity
+        self.entries = []   # (key, tensor ref, sorted row, permutation or None)
+
+    def get(self, pos):
+        key = (pos.data_ptr(), pos.numel(), _version_of(pos), pos.device)
+        for k, _, srt, perm in self.entries:
+            if k == key:
+                return srt, perm
+        row = pos.detach().contiguous()
+        srt, perm = torch.sort(row, stable=True)
+        if torch.cuda.is_current_stream_capturing():
+            return srt, perm
+        if bool((perm == torch.arange(perm.numel(), device=perm.device)).all()):
+            srt, perm = row, None
+        self.entries.append((key, pos, srt, perm))   # the tensor ref pins the storage behind data_ptr
+        if len(self.entries) > self.capacity:
+            self.entries.pop(0)
+        return srt, perm
+
+
+_f64_grids = _SortedGridCache()
+
+
+def _f64_row_losses(x, y, xpos, ypos, p, flags):
+    """The float64 route behind Wasserstein1D and wasserstein_1d (_f64_route_applies holds): flat [rows] float64 losses.  The kernels take
+    sorted supports, so SOT_FLAG_REQUIRE_SORT is served here: a shared grid is sorted once per tensor version (_SortedGridCache; a grid
+    that is sorted already -- the common case -- adds no torch kernel in front of the HIP call), per-row positions per call; the weights
+    follow through differentiable gathers."""
+    n, m = x.shape[-1], y.shape[-1]
+    x2 = nat.rows_view(x.reshape(-1, n))
+    y2 = nat.rows_view(y.reshape(-1, m))
+    sort = bool(flags & nat.FLAG_REQUIRE_SORT)
+    if _is_shared_row(xpos):
+        xp = xpos if xpos.ndim == 1 else xpos.reshape(-1, n)[0]
+        yp = ypos if ypos.ndim == 1 else ypos.reshape(-1, m)[0]
+        if sort:
+            xp, xperm = _f64_grids.get(xp)
+            yp, yperm = _f64_grids.get(yp)
+            if xperm is not None:
+                x2 = x2.index_select(1, xperm)
+            if yperm is not None:
+                y2 = y2.index_select(1, yperm)
+        else:
+            xp, yp = xp.detach().contiguous(), yp.detach().contiguous()
+    else:
+        xp, yp = xpos.detach().reshape(-1, n), ypos.detach().reshape(-1, m)
+        if sort:
+            xp, xi = torch.sort(xp, dim=1, stable=True)
+            yp, yi = torch.sort(yp, dim=1, stable=True)
+            x2, y2 = torch.gather(x2, 1, xi), torch.gather(y2, 1, yi)
+        else:
+            xp, yp = xp.contiguous(), yp.contiguous()
+    fl = int(flags) & _F64_FLAGS
+    if torch.is_grad_enabled() and (x2.requires_grad or y2.requires_grad):
+        return _RowLossF64.apply(x2, y2, xp, yp, float(p), fl)
+    return nat.forward_rows_f64(x2, y2, xp, yp, float(p), fl)
 
 
 MIXED_ROUTE = True   # module switch (tests and tools/bench_mixed.py compare both routes): False = mixed supports are materialised as before
@@ -534,6 +656,8 @@ def wasserstein_1d(u_values, v_values, u_weights=None, v_weights=None, p=1, requ
         u_weights = torch.full(u_values.shape, 1.0 / n, device=u_values.device, dtype=u_values.dtype)
     if v_weights is None:
         v_weights = torch.full(v_values.shape, 1.0 / m, device=v_values.device, dtype=v_values.dtype)
+    if u_weights.dtype is torch.float64 and _f64_route_applies(u_weights, v_weights, u_values, v_values, return_quantiles):
+        return _f64_row_losses(u_weights, v_weights, u_values, v_values, p, _flags(False, False, limit_quantile_range, require_sort, prenormalized=True))
     if not _hip_domain(u_weights, v_weights, u_values, v_values) or _beyond_one_cu(u_weights, v_weights, u_values, v_values):
         if u_weights.is_cuda and u_weights.dtype is torch.bfloat16:   # (rows beyond one CU's LDS: the composition on the upcast weights)
             u_weights, v_weights = u_weights.float(), v_weights.float()
@@ -712,10 +836,19 @@ class Wasserstein1D(torch.nn.Module):
             dims=(0 if rows_only else kwargs.get("dims", None)), return_quantiles=(not rows_only) and kwargs.get("return_quantiles", False),
             rows_only=rows_only)
 
+    def _f64_rows(self, x, y, x_pos_, y_pos_, kwargs):
+        """float64 GPU tensors on the float64 kernels (_f64_route_applies holds): the flat row losses after the optional hinge."""
+        loss = _f64_row_losses(x, y, x_pos_, y_pos_, self.p, self._flag_word(kwargs))
+        if self.hinge:
+            loss = torch.nn.functional.relu(loss - kwargs.get("hinge", 0.0))
+        return loss
+
     def row_losses(self, x, y, x_pos=None, y_pos=None, **kwargs):
         """Flat [rows] tensor of W_p^p per spectrum pair (after the optional hinge, before the mean):
         what losses.py:186-205 holds before its reshape/mean.  Used by the row-sharded multi-GPU path."""
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
+        if x.dtype is torch.float64 and _f64_route_applies(x, y, x_pos_, y_pos_):
+            return self._f64_rows(x, y, x_pos_, y_pos_, kwargs)
         if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
             return self._torch_forward(x, y, x_pos_, y_pos_, kwargs, rows_only=True)
         if x.dtype is torch.bfloat16 and not (_typed_forward_applies(x, y, x_pos_, y_pos_)
@@ -777,6 +910,10 @@ class Wasserstein1D(torch.nn.Module):
                         and not (torch.is_grad_enabled() and (x2.requires_grad or xp.requires_grad or yp.requires_grad))):
                     return hot.glue.mean_loss_fresh(x2, y2, xp, yp, float(self.p), hot.flags_no_same_grid | (nat.FLAG_SAME_GRID if (xp is yp and hot.area_ok) else 0))
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
+        if x.dtype is torch.float64 and _f64_route_applies(x, y, x_pos_, y_pos_, kwargs.get("return_quantiles", False)):
+            # the float64 kernels; hinge, dims and the mean stay torch ops on the float64 row losses (losses.py:203-211)
+            loss = self._f64_rows(x, y, x_pos_, y_pos_, kwargs)
+            return torch.mean(loss.reshape(x.shape[:-1]), dim=kwargs.get("dims", None))
         if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
             return self._torch_forward(x, y, x_pos_, y_pos_, kwargs)
         if x.dtype is torch.bfloat16:

@@ -32,13 +32,15 @@
 extern "C" {
 #endif
 
-#define SOT_ABI_VERSION 20   /* bumped on every change of a signature or of a buffer contract below; the binding checks it
+#define SOT_ABI_VERSION 21  /* bumped on every change of a signature or of a buffer contract below; the binding checks it
                               * (11, round 6: sot_workspace_bytes covers the per-row pre-sort; the MSS workspace is 16-byte aligned;
                               *  14: sot_w1d_quantiles_backward; 15: sot_fir_*; 16: sot_spec_metrics; 17: sot_w1d_mixed_*;
                               *  18: sot_workspace_bytes is 0 for per-row positions outside the pre-sort's domain;
                               *  19: bfloat16 weight rows -- sot_rows_bf16_to_f32, sot_rows_f32_to_bf16, sot_w1d_*_bf16;
                               *  20: bfloat16 training -- sot_w1d_backward_bf16, sot_w1d_loss_and_grad_bf16, sot_w1d_bf16_native,
-                              *      sot_w1d_bf16_backward_workspace_bytes) */
+                              *      sot_w1d_bf16_backward_workspace_bytes;
+                              *  21: float64 rows -- sot_problem_f64, sot_w1d_forward_f64, sot_w1d_backward_f64, sot_w1d_f64_supported,
+                              *      sot_w1d_f64_workspace_bytes) */
 
 typedef enum sot_status {
     SOT_OK = 0,
@@ -392,6 +394,50 @@ extern int sot_w1d_backward_bf16(const sot_problem *prob, const float *grad_row,
 extern int sot_w1d_loss_and_grad_bf16(const sot_problem *prob, float *row_loss /* [B] */, double denom, float *mean_out, double *sum_out,
                                       float grad_scale, uint16_t *grad_y /* [B,m] */, uint32_t *completion_counters /* or NULL */,
                                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- float64 rows (ABI 21; csrc/sot_f64.hip): the row pipeline in double precision -- what torch.autograd.gradcheck and a model trained in
+ * double hand over.  The reference in float64 is plain ATen on double tensors (losses.py:129-313); these calls evaluate SURVEY.md A.1 / A.2 / A.4
+ * in double with every sum in a fixed order (thread chunk, wavefront, the workgroup's wavefronts in order), so a row's result depends neither
+ * on the grid nor on its place in the batch.  Not bit-identical to ATen's float64 (another summation order: ~1e-15 relative without the
+ * cutoff; under SOT_FLAG_LIMIT_Q a level that sits on the edge 1 by its last bit is kept or dropped with that bit).
+ *   sot_problem_f64: the fields of sot_problem with double data and a double p; no plan and no permutation fields.
+ *   Supports must arrive SORTED (positions non-decreasing along each row; shared positions: row stride 0 on both sides, per-row: on both):
+ *     a problem with SOT_FLAG_REQUIRE_SORT is refused (SOT_ERR_BAD_SHAPE) -- the caller sorts.  Flags honoured: SQUARE, DONT_NORMALIZE,
+ *     LIMIT_Q, PRENORMALIZED; the others are ignored.  Mass guard: a mass <= 1e-7 (compared as a double) is replaced by the float32 value
+ *     1e-7 widened to double (utils.py:135-142).
+ *   sot_w1d_forward_f64: row_loss[r] = W_p^p of row pair r.
+ *   sot_w1d_backward_f64: grad_x / grad_y (dense [B, n] / [B, m]; either may be NULL and is then not computed) = d sum_r grad_row[r *
+ *     grad_row_stride] * grad_scale * loss_r / d x, d y; grad_row_stride is 0 or 1, grad_row == NULL means 1 for every row.  At exactly tied
+ *     levels the gradient of a run of equal levels goes to the run's last member in the stable order (U before V, lower index first): the tie
+ *     order of sot_w1d_backward.
+ *   Sizes: one row pair's working set lives in one CU's LDS -- 16 (n + m) bytes forward (n + m <= 10 000 at least; 4097 + 4097 fits), 24 (n + m)
+ *     bytes backward (n + m <= 6 600 at least).  Beyond: SOT_ERR_UNSUPPORTED_SIZE.  sot_w1d_f64_supported(prob, backward): 1 where the forward
+ *     (backward != 0: the backward) takes the problem, 0 otherwise -- NULL, bad shapes or strides, p < 1, REQUIRE_SORT, size; host arithmetic.
+ *   sot_w1d_f64_workspace_bytes: 0 for every problem of this ABI version (the calls use no workspace; the argument pair is kept for the
+ *     calling convention of the library).  A workspace_bytes > 0 with workspace == NULL is refused (SOT_ERR_NULL_POINTER).
+ *   Every refusal is decided before anything is enqueued; B == 0 returns SOT_OK.  (The three int calls are declared `extern` for the reason
+ *   given above; their guard-band cases, refusals and empty batches are in tests/test_f64_gpu.py, and the binding lists them in
+ *   _native.F64_EXPORTS.) */
+typedef struct sot_problem_f64 {
+    const double *x;          /* [B, n] weights of the first measure                                  */
+    const double *y;          /* [B, m] weights of the second measure                                 */
+    const double *xpos;       /* sorted support positions of x: [n] (row stride 0) or [B, n]          */
+    const double *ypos;       /* sorted support positions of y: [m] (row stride 0) or [B, m]          */
+    int64_t B;
+    int32_t n, m;
+    int64_t x_row_stride;     /* elements between consecutive rows (>= n / >= m)                      */
+    int64_t y_row_stride;
+    int64_t xpos_row_stride;  /* 0 = one shared position row, otherwise >= n / >= m                   */
+    int64_t ypos_row_stride;
+    double p;                 /* p >= 1; the result is W_p^p                                          */
+    uint32_t flags;           /* SOT_FLAG_*                                                           */
+} sot_problem_f64;
+size_t sot_w1d_f64_workspace_bytes(const sot_problem_f64 *prob);
+extern int sot_w1d_f64_supported(const sot_problem_f64 *prob, int backward);
+extern int sot_w1d_forward_f64(const sot_problem_f64 *prob, double *row_loss /* [B] */, void *workspace, size_t workspace_bytes, void *stream);
+extern int sot_w1d_backward_f64(const sot_problem_f64 *prob, const double *grad_row, int64_t grad_row_stride, double grad_scale,
+                                double *grad_x /* [B,n] or NULL */, double *grad_y /* [B,m] or NULL */, void *workspace, size_t workspace_bytes,
+                                void *stream);
 
 /* out[c] = sum_r rows[r * row_stride + c], c < n, in a fixed order with fp64 accumulation (B == 0: zeros). */
 int sot_column_sum(const float *rows, int64_t B, int32_t n, int64_t row_stride, float *out /* [n] */, void *stream);
