@@ -334,28 +334,34 @@ def row_permutations(x, y, xpos, ypos, flags):
     return torch.empty((x.shape[0], x.shape[1] + y.shape[1]), dtype=torch.uint16, device=x.device)
 
 
-def make_problem(x, y, xpos, ypos, p, flags, plan=None, perm_out=None, perm_in=None) -> SotProblem:
+def _fill_geometry(pr, x, y, xpos, ypos, shared=False, dense=False):
+    """B, n, m and the four row strides of a sot_problem / sot_problem_f64 from 2-D weight rows and positions (tensors of any device: only
+    shapes and strides are read).  One row's stride is its length; a 1-D position row -- or any, once planned (shared) -- has stride 0;
+    dense: per-row positions are described as dense rows whatever their strides (bf16_native's question is about the weights)."""
     B, n = x.shape
     m = y.shape[1]
+    pr.B, pr.n, pr.m = B, n, m
+    pr.x_row_stride = x.stride(0) if B > 1 else n
+    pr.y_row_stride = y.stride(0) if B > 1 else m
+    pr.xpos_row_stride = 0 if (shared or xpos.ndim == 1) else (xpos.stride(0) if (B > 1 and not dense) else n)
+    pr.ypos_row_stride = 0 if (shared or ypos.ndim == 1) else (ypos.stride(0) if (B > 1 and not dense) else m)
+
+
+def make_problem(x, y, xpos, ypos, p, flags, plan=None, perm_out=None, perm_in=None) -> SotProblem:
     pr = SotProblem()
     pr.row_perm_out = perm_out.data_ptr() if perm_out is not None else None
     pr.row_perm_in = perm_in.data_ptr() if perm_in is not None else None
     if plan is not None:
         plan.use_on_current_stream(x.device)
     pr.x, pr.y = x.data_ptr(), y.data_ptr()
-    pr.B, pr.n, pr.m = B, n, m
-    pr.x_row_stride = x.stride(0) if B > 1 else n
-    pr.y_row_stride = y.stride(0) if B > 1 else m
+    _fill_geometry(pr, x, y, xpos, ypos, shared=plan is not None)
     pr.p, pr.flags = float(p), problem_flags(p, flags, plan)
     if plan is not None:
         pr.xpos, pr.ypos = plan.xpos_sorted.data_ptr(), plan.ypos_sorted.data_ptr()
         pr.xperm, pr.yperm = plan.xperm.data_ptr(), plan.yperm.data_ptr()
         pr.perm_is_identity = plan.ident.data_ptr()
-        pr.xpos_row_stride = pr.ypos_row_stride = 0
     else:
         pr.xpos, pr.ypos = xpos.data_ptr(), ypos.data_ptr()
-        pr.xpos_row_stride = 0 if xpos.ndim == 1 else (xpos.stride(0) if B > 1 else n)
-        pr.ypos_row_stride = 0 if ypos.ndim == 1 else (ypos.stride(0) if B > 1 else m)
         pr.xperm = pr.yperm = pr.perm_is_identity = None
     return pr
 
@@ -475,8 +481,9 @@ def workspace(pr: SotProblem, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
 
 
-# ---- the four calls on weight rows, each ONE marshalling helper for both element types.  What a pair differs by is passed in: the C function,
-# the dtype of the gradient rows, and the workspace query ws(pr, dev, flags, plan, need_gx, need_gy).
+# ---- the four calls on weight rows, each ONE marshalling helper for every element type.  What the calls differ by is passed in: the C function,
+# the dtype of the gradient rows (and, for float64, of the row losses), the workspace query ws(pr, dev, flags, plan, need_gx, need_gy) and the
+# problem maker (make_problem, or the float64 struct's).
 
 def _grad_row_arg(grad_row, B):
     """(contiguous tensor, element stride 0 / 1) of an upstream row gradient: [B], or one element that is broadcast to every row."""
@@ -492,10 +499,10 @@ def _ws_f32(pr, dev, flags, plan, need_gx=False, need_gy=False):
     return workspace(pr, dev) if _needs_workspace(pr, flags, plan) else None
 
 
-def _forward_rows(fn, ws_of, x, y, xpos, ypos, p, flags, plan, out=None, perm_out=None, perm_in=None):
+def _forward_rows(fn, ws_of, x, y, xpos, ypos, p, flags, plan, out=None, perm_out=None, perm_in=None, problem=make_problem, dtype=torch.float32):
     dev = x.device
-    row_loss = out if out is not None else torch.empty(x.shape[0], dtype=torch.float32, device=dev)
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_out, perm_in)
+    row_loss = out if out is not None else torch.empty(x.shape[0], dtype=dtype, device=dev)
+    pr = problem(x, y, xpos, ypos, p, flags, plan, perm_out, perm_in)
     ws = ws_of(pr, dev, flags, plan)
     with _on_device(dev):
         rc = fn(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
@@ -535,14 +542,15 @@ def _loss_and_grad(fn, grad_dtype, ws_of, x, y, xpos, ypos, p, flags, plan, fuse
     return mean, row_loss, gy
 
 
-def _backward_rows(fn, grad_dtype, ws_of, x, y, xpos, ypos, p, flags, grad_row, need_gx, need_gy, plan, grad_scale, perm_in=None, gy_out=None, extra=()):
+def _backward_rows(fn, grad_dtype, ws_of, x, y, xpos, ypos, p, flags, grad_row, need_gx, need_gy, plan, grad_scale, perm_in=None, gy_out=None, extra=(),
+                   problem=make_problem):
     """grad_row: _grad_row_arg()'s pair; extra: the arguments of the C function between the gradient pointers and the workspace (the typed call's rescale)."""
     dev = x.device
     B, n = x.shape
     m = y.shape[1]
     gx = torch.empty(B, n, dtype=grad_dtype, device=dev) if need_gx else None
     gy = (gy_out if gy_out is not None else torch.empty(B, m, dtype=grad_dtype, device=dev)) if need_gy else None
-    pr = make_problem(x, y, xpos, ypos, p, flags, plan, perm_in=perm_in)
+    pr = problem(x, y, xpos, ypos, p, flags, plan, perm_in=perm_in)
     ws = ws_of(pr, dev, flags, plan, need_gx, need_gy)
     g, stride = grad_row
     with _on_device(dev):
@@ -640,11 +648,7 @@ def bf16_native(x, y, xpos, ypos, p, flags, plan=None) -> bool:
     flags and the alignment of the two weight pointers -- no device is touched, so CPU or meta stand-ins answer too)?  x, y: 2-D weight rows
     as the native calls take them; positions: 1-D when shared."""
     pr = SotProblem()
-    pr.B, pr.n, pr.m = x.shape[0], x.shape[1], y.shape[1]
-    pr.x_row_stride = x.stride(0) if pr.B > 1 else pr.n
-    pr.y_row_stride = y.stride(0) if pr.B > 1 else pr.m
-    pr.xpos_row_stride = 0 if (plan is not None or xpos.ndim == 1) else pr.n
-    pr.ypos_row_stride = 0 if (plan is not None or ypos.ndim == 1) else pr.m
+    _fill_geometry(pr, x, y, xpos, ypos, shared=plan is not None, dense=True)
     pr.x, pr.y = x.data_ptr(), y.data_ptr()
     pr.p, pr.flags = float(p), int(flags)
     return bool(load().sot_w1d_bf16_native(ctypes.byref(pr)))
@@ -679,18 +683,13 @@ def loss_and_grad_bf16(x, y, xpos, ypos, p, flags, plan=None, fused_mean=None):
 
 # ---- float64 rows (ABI 21; csrc/sot_f64.hip): double weights, double positions, double row losses and gradients.  Supports arrive sorted.
 
-def make_problem_f64(x, y, xpos, ypos, p, flags) -> SotProblemF64:
+def make_problem_f64(x, y, xpos, ypos, p, flags, plan=None, perm_out=None, perm_in=None) -> SotProblemF64:
     """The sot_problem_f64 of 2-D weight rows (unit inner stride) and sorted positions, 1-D on both sides (shared) or [B, .] on both.  Only
-    shapes, strides and data pointers are read, so CPU or meta stand-ins can be described too (f64_supported)."""
-    B, n = x.shape
-    m = y.shape[1]
+    shapes, strides and data pointers are read, so CPU or meta stand-ins can be described too.  plan, perm_out, perm_in: the marshalling helpers' arguments of
+    make_problem, unused here (sorted supports: no plan, no permutations)."""
     pr = SotProblemF64()
     pr.x, pr.y, pr.xpos, pr.ypos = x.data_ptr(), y.data_ptr(), xpos.data_ptr(), ypos.data_ptr()
-    pr.B, pr.n, pr.m = B, n, m
-    pr.x_row_stride = x.stride(0) if B > 1 else n
-    pr.y_row_stride = y.stride(0) if B > 1 else m
-    pr.xpos_row_stride = 0 if xpos.ndim == 1 else (xpos.stride(0) if B > 1 else n)
-    pr.ypos_row_stride = 0 if ypos.ndim == 1 else (ypos.stride(0) if B > 1 else m)
+    _fill_geometry(pr, x, y, xpos, ypos)
     pr.p, pr.flags = float(p), int(flags)
     return pr
 
@@ -699,7 +698,7 @@ def f64_supported(n, m, backward=False, p=1.0, flags=0, per_row=False) -> bool:
     """Do the float64 calls take rows of n and m points (sot_w1d_f64_supported: host arithmetic, no device is touched)?  backward: the
     backward's larger working set."""
     pr = SotProblemF64()
-    pr.B, pr.n, pr.m = 1, int(n), int(m)
+    pr.B, pr.n, pr.m = 1, int(n), int(m)   # (no tensors to read: one dense row pair)
     pr.x_row_stride, pr.y_row_stride = int(n), int(m)
     pr.xpos_row_stride, pr.ypos_row_stride = (int(n), int(m)) if per_row else (0, 0)
     pr.p, pr.flags = float(p), int(flags)
@@ -712,7 +711,7 @@ def _require_f64(*tensors):
             raise TypeError(f"the float64 calls take float64 GPU tensors; got {t.dtype} on {t.device}")
 
 
-def _f64_workspace(pr, dev):
+def _f64_workspace(pr, dev, flags=None, plan=None, need_gx=False, need_gy=False):
     nbytes = int(load().sot_w1d_f64_workspace_bytes(ctypes.byref(pr)))
     return torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes > 0 else None
 
@@ -721,33 +720,16 @@ def forward_rows_f64(x, y, xpos, ypos, p, flags) -> torch.Tensor:
     """row_loss[B] (float64) = W_p^p per row for float64 weights and sorted float64 positions (sot_w1d_forward_f64)."""
     lib = load()
     _require_f64(x, y, xpos, ypos)
-    dev = x.device
-    row_loss = torch.empty(x.shape[0], dtype=torch.float64, device=dev)
-    pr = make_problem_f64(x, y, xpos, ypos, p, flags)
-    ws = _f64_workspace(pr, dev)
-    with _on_device(dev):
-        rc = lib.sot_w1d_forward_f64(ctypes.byref(pr), row_loss.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return row_loss
+    return _forward_rows(lib.sot_w1d_forward_f64, _f64_workspace, x, y, xpos, ypos, p, flags, None, problem=make_problem_f64, dtype=torch.float64)
 
 
 def backward_rows_f64(x, y, xpos, ypos, p, flags, grad_row, need_gx=True, need_gy=True, grad_scale=1.0):
     """(gx, gy) in float64 (sot_w1d_backward_f64).  grad_row: float64, [B] or one broadcast element, or None (1 for every row)."""
     lib = load()
     _require_f64(x, y, xpos, ypos, grad_row)
-    dev = x.device
-    B, n = x.shape
-    m = y.shape[1]
-    gx = torch.empty(B, n, dtype=torch.float64, device=dev) if need_gx else None
-    gy = torch.empty(B, m, dtype=torch.float64, device=dev) if need_gy else None
-    pr = make_problem_f64(x, y, xpos, ypos, p, flags)
-    ws = _f64_workspace(pr, dev)
-    g, stride = (None, 0) if grad_row is None else _grad_row_arg(grad_row, B)
-    with _on_device(dev):
-        rc = lib.sot_w1d_backward_f64(ctypes.byref(pr), _ptr(g), stride, float(grad_scale), _ptr(gx), _ptr(gy), _ptr(ws),
-                                      ws.numel() if ws is not None else 0, stream_ptr(dev))
-    check(rc, p)
-    return gx, gy
+    g = (None, 0) if grad_row is None else _grad_row_arg(grad_row, x.shape[0])   # None: 1 for every row
+    return _backward_rows(lib.sot_w1d_backward_f64, torch.float64, _f64_workspace, x, y, xpos, ypos, p, flags, g, need_gx, need_gy, None, grad_scale,
+                          problem=make_problem_f64)
 
 
 def prepared_loss_call(x, y, xpos, ypos, p, flags, plan, row_out, mean_out, sum_out=None, stream=None):

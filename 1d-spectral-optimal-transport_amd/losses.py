@@ -7,14 +7,10 @@ Same names, argument meaning and error behaviour as the reference's ``losses`` m
 (utils.py:135-142), so ``trainer.py:220/228``, ``metrics.py:148`` and the YAML
 ``class_path: losses.Wasserstein1D`` keep working unchanged.
 
-All arithmetic on float32 HIP-device tensors runs in the hand-written HIP library (csrc/, C ABI in
-include/sot_hip.h); this file only reshapes, marshals pointers and wires autograd.  bfloat16 weights on the device (autocast) are
-the float32 call on the exactly widened rows: the typed forward where no gradient is asked for; where one is, the typed backward and
-training form on the rows that have 16-bit backward kernels (_typed_training_applies), a widening kernel in front of the float32 path
--- and a narrowing one behind its gradient -- elsewhere (_hip_domain).  float64 weights on float64 positions run the float64 kernels
-(csrc/sot_f64.hip) where _f64_route_applies holds.  Tensors outside the library's domain
--- CPU tensors, float64 outside that gate -- take the reference's own route, torch ops (_torch_path.py), because the reference is device- and
-dtype-agnostic (losses.py:129-211) and `accelerator: cpu` has to keep working.
+All arithmetic on HIP-device tensors runs in the hand-written HIP library (csrc/, C ABI in include/sot_hip.h); this file only reshapes,
+marshals pointers and wires autograd.  Which kernels a call reaches is decided once per call by _route(); the table "condition -> route
+-> native calls" is DESIGN.md section 1.1.  Tensors outside the library's domain take the reference's own route, torch ops
+(_torch_path.py), because the reference is device- and dtype-agnostic (losses.py:129-211) and `accelerator: cpu` has to keep working.
 """
 from __future__ import annotations
 
@@ -54,6 +50,11 @@ def warn_once(key, message):
         warnings.warn(message, stacklevel=3)
 
 
+def _is_hip_tensor(t) -> bool:
+    """The one device test of the route decision (tests patch it to run the decision on meta stand-ins)."""
+    return t.is_cuda
+
+
 def _hip_domain(x, y, *positions) -> bool:
     """True when the HIP library takes these tensors (the two weight tensors first, then the positions): all of them on a HIP device, the
     positions float32 and the weights either both float32 or both bfloat16 -- what a model under torch.autocast(dtype=torch.bfloat16)
@@ -63,13 +64,14 @@ def _hip_domain(x, y, *positions) -> bool:
     float64 GPU tensor says so once.  half GPU tensors (another exponent range), a float32 / bfloat16 mix and bfloat16 positions are
     refused (TypeError), not upcast."""
     ts = [t for t in (x, y) + positions if t is not None]
-    if all(t.is_cuda for t in ts) and all(t.dtype == torch.float32 for t in positions if t is not None):
+    on_hip = [_is_hip_tensor(t) for t in ts]
+    if all(on_hip) and all(t.dtype == torch.float32 for t in positions if t is not None):
         if x.dtype == y.dtype and x.dtype in (torch.float32, torch.bfloat16):
             return True
-    for t in ts:
-        if t.is_cuda and t.dtype in (torch.float16, torch.bfloat16):
+    for t, hip in zip(ts, on_hip):
+        if hip and t.dtype in (torch.float16, torch.bfloat16):
             raise TypeError(f"sot_amd computes in float32; got {t.dtype} (convert with .float())")
-    if any(t.is_cuda for t in ts):
+    if any(on_hip):
         warn_once("not-hip-f32", "sot_amd: tensors that are not all float32 on the GPU (float64, or CPU and GPU mixed) run the torch-op "
                                  "composition in their own dtype, like the reference; the HIP kernels take float32 GPU tensors")
     return False
@@ -94,29 +96,30 @@ def _widen(t):
     return out.reshape(t.shape)
 
 
-def _typed_forward_applies(x, y, xpos, ypos, return_quantiles=False) -> bool:
+def _typed_forward_applies(x, y, xpos, ypos, return_quantiles=False, mixed=None) -> bool:
     """bfloat16 weights: does the call take the typed forward (sot_w1d_forward_bf16 / sot_w1d_loss_bf16 -- 16-bit row loads in the kernel on
     the headline and paper shapes, widening inside the call elsewhere)?  Calls that need no gradient do: torch.no_grad, inference_mode,
     operands without requires_grad.  Calls that need one take the typed training calls where _typed_training_applies holds; the others,
-    return_quantiles and the mixed-supports route widen x and y first (_widen) and follow the float32 path unchanged."""
-    if return_quantiles or mixed_route_applies(x, y, xpos, ypos):
+    return_quantiles and the mixed-supports route widen x and y first (_widen) and follow the float32 path unchanged.  mixed: the answer of
+    mixed_route_applies where the caller has it already (_route)."""
+    if return_quantiles or (mixed_route_applies(x, y, xpos, ypos) if mixed is None else mixed):
         return False
     return not (torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)))
 
 
-def _typed_training_applies(x, y, xpos, ypos, return_quantiles=False, flags=0, p=1.0) -> bool:
+def _typed_training_applies(x, y, xpos, ypos, return_quantiles=False, flags=0, p=1.0, mixed=None) -> bool:
     """bfloat16 weights that ask for a gradient: does the call take the typed backward / training form (sot_w1d_backward_bf16 /
     sot_w1d_loss_and_grad_bf16 -- 16-bit row loads and 16-bit gradient stores inside the backward kernels, no float32 image of a spectrum or
     of a gradient)?  It does when x or y requires a gradient and neither position tensor does, outside return_quantiles, the mixed-supports
     route and compiled calls, on the problems those kernels exist for (nat.bf16_native: shared positions, 512 / 1024 / 2048 / 4096 bins,
     16-byte aligned rows, not the opt-in tie-free form).  Everything else keeps the _widen route: there the C call would widen on the forward
     AND on the backward, two conversions more than _widen's.  A function of dtypes, shapes, strides, requires_grad, the grad mode, the flag
-    word and the alignment of the two data pointers: no device is touched."""
+    word and the alignment of the two data pointers: no device is touched.  mixed: as in _typed_forward_applies."""
     if _compiling() or x.dtype is not torch.bfloat16 or y.dtype is not torch.bfloat16 or not torch.is_grad_enabled():
         return False
     if not (x.requires_grad or y.requires_grad) or xpos.requires_grad or ypos.requires_grad:
         return False
-    if return_quantiles or xpos.ndim != 1 or ypos.ndim != 1 or mixed_route_applies(x, y, xpos, ypos):
+    if return_quantiles or xpos.ndim != 1 or ypos.ndim != 1 or (mixed_route_applies(x, y, xpos, ypos) if mixed is None else mixed):
         return False
     if x.ndim < 2 or y.ndim < 2 or x.shape[-1] != xpos.shape[0] or y.shape[-1] != ypos.shape[0]:
         return False    # (the general path says what is wrong with such a call)
@@ -202,15 +205,34 @@ def _position_grads_torch(x, y, xpos, ypos, p, flags, plan, grad_rows, need_x, n
     return out
 
 
+# element type of the weight rows -> (forward, backward, dtype of the row cotangents) of _RowLoss.  The functions are looked up on `nat` by
+# name at call time (tests wrap them there).
+_ROW_CALLS = {torch.float32: ("forward_rows", "backward_rows", torch.float32),
+              torch.bfloat16: ("forward_rows_bf16", "backward_rows_bf16", torch.float32),
+              torch.float64: ("forward_rows_f64", "backward_rows_f64", torch.float64)}
+
+
+def _forward_rows(x, y, xpos, ypos, p, flags, plan, perm_out=None):
+    """The plain row-loss call of x's element type (the float64 call takes sorted supports and no plan; only float32 rows leave permutations)."""
+    fn = getattr(nat, _ROW_CALLS[x.dtype][0])
+    if x.dtype is torch.float64:
+        return fn(x, y, xpos, ypos, p, flags)
+    return fn(x, y, xpos, ypos, p, flags, plan) if perm_out is None else fn(x, y, xpos, ypos, p, flags, plan, perm_out=perm_out)
+
+
 class _RowLoss(torch.autograd.Function):
-    """rows[B] = W_p^p per spectrum pair; backward = closed-form HIP kernel.  Per-row positions (the `torch.sort(u_values, 1)`
-    of losses.py:286-288 on every row) are sorted ONCE per step: the forward leaves each row's permutations in a uint16 buffer and the
+    """rows[B] = W_p^p per spectrum pair in the element type of the weight rows (_ROW_CALLS); backward = the closed-form HIP kernel of that
+    type, only the gradients asked for.  bfloat16 rows come here where _typed_training_applies holds and float64 rows where
+    _f64_route_applies does, so row permutations and position gradients are float32-only: per-row positions (the `torch.sort(u_values, 1)`
+    of losses.py:286-288 on every row) are sorted ONCE per step -- the forward leaves each row's permutations in a uint16 buffer and the
     backward / position-gradient kernels gather through them (sot_problem.row_perm_out / row_perm_in)."""
 
     @staticmethod
     def forward(ctx, x, y, xpos, ypos, p, flags, plan):
-        perm = nat.row_permutations(x, y, xpos, ypos, flags) if (plan is None and any(ctx.needs_input_grad[:4])) else None
-        rows = nat.forward_rows(x, y, xpos, ypos, p, flags, plan, perm_out=perm)
+        perm = None
+        if x.dtype is torch.float32 and plan is None and any(ctx.needs_input_grad[:4]):
+            perm = nat.row_permutations(x, y, xpos, ypos, flags)
+        rows = _forward_rows(x, y, xpos, ypos, p, flags, plan, perm)
         ctx.save_for_backward(x, y, xpos, ypos, *([perm] if perm is not None else []))
         ctx.p, ctx.flags, ctx.plan = p, flags, plan
         return rows
@@ -218,61 +240,34 @@ class _RowLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_rows):
         x, y, xpos, ypos, *perm = ctx.saved_tensors
-        perm = perm[0] if perm else None
+        _, backward, cotangent = _ROW_CALLS[x.dtype]
+        grad_rows = grad_rows.to(cotangent)
+        extra = {} if x.dtype is torch.float64 else {"plan": ctx.plan}
+        if perm:
+            extra["perm_in"] = perm[0]
         gx = gy = gxp = gyp = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            gx, gy = nat.backward_rows(x, y, xpos, ypos, ctx.p, ctx.flags, grad_rows.float(),
-                                       need_gx=ctx.needs_input_grad[0], need_gy=ctx.needs_input_grad[1], plan=ctx.plan, perm_in=perm)
+            gx, gy = getattr(nat, backward)(x, y, xpos, ypos, ctx.p, ctx.flags, grad_rows, need_gx=ctx.needs_input_grad[0],
+                                            need_gy=ctx.needs_input_grad[1], **extra)
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            gxp, gyp = _position_grads(x, y, xpos, ypos, ctx.p, ctx.flags, ctx.plan, grad_rows.float(), ctx.needs_input_grad[2],
-                                       ctx.needs_input_grad[3], perm_in=perm)
+            gxp, gyp = _position_grads(x, y, xpos, ypos, ctx.p, ctx.flags, ctx.plan, grad_rows, ctx.needs_input_grad[2],
+                                       ctx.needs_input_grad[3], perm_in=extra.get("perm_in"))
         return gx, gy, gxp, gyp, None, None, None
 
 
-class _RowLossBF16(torch.autograd.Function):
-    """_RowLoss for bfloat16 weights where _typed_training_applies holds (shared positions that ask for no gradient): the typed forward, and
-    the typed backward with the row cotangents -- the float32 node's arguments, each gradient element its float32 element rounded once."""
-
-    @staticmethod
-    def forward(ctx, x, y, xpos, ypos, p, flags, plan):
-        rows = nat.forward_rows_bf16(x, y, xpos, ypos, p, flags, plan)
-        ctx.save_for_backward(x, y, xpos, ypos)
-        ctx.p, ctx.flags, ctx.plan = p, flags, plan
-        return rows
-
-    @staticmethod
-    def backward(ctx, grad_rows):
-        x, y, xpos, ypos = ctx.saved_tensors
-        gx, gy = nat.backward_rows_bf16(x, y, xpos, ypos, ctx.p, ctx.flags, grad_rows.float(), need_gx=ctx.needs_input_grad[0],
-                                        need_gy=ctx.needs_input_grad[1], plan=ctx.plan)
-        return gx, gy, None, None, None, None, None
+class _RowLossBF16(_RowLoss):
+    """_RowLoss under the grad_fn name the typed training route has always shown (tests/golden/host_routes.json pins it)."""
 
 
-class _RowLossF64(torch.autograd.Function):
-    """rows[B] = W_p^p per pair in float64 (sot_w1d_forward_f64) on sorted supports that ask for no gradient; backward: the closed form in
-    double (sot_w1d_backward_f64), only the gradients asked for."""
+class _RowLossF64(_RowLoss):
+    """_RowLoss under the grad_fn name of the float64 route."""
 
-    @staticmethod
-    def forward(ctx, x, y, xpos, ypos, p, flags):
-        rows = nat.forward_rows_f64(x, y, xpos, ypos, p, flags)
-        ctx.save_for_backward(x, y, xpos, ypos)
-        ctx.p, ctx.flags = p, flags
-        return rows
 
-    @staticmethod
-    def backward(ctx, grad_rows):
-        x, y, xpos, ypos = ctx.saved_tensors
-        gx, gy = nat.backward_rows_f64(x, y, xpos, ypos, ctx.p, ctx.flags, grad_rows.double(), need_gx=ctx.needs_input_grad[0],
-                                       need_gy=ctx.needs_input_grad[1])
-        return gx, gy, None, None, None, None
+_ROW_NODES = {torch.float32: _RowLoss, torch.bfloat16: _RowLossBF16, torch.float64: _RowLossF64}
 
 
 F64_ROUTE = True   # module switch (tools/bench_f64.py times both routes): False = float64 GPU tensors run the torch-op composition as before
 _F64_FLAGS = nat.FLAG_SQUARE | nat.FLAG_DONT_NORMALIZE | nat.FLAG_LIMIT_Q | nat.FLAG_PRENORMALIZED   # what the float64 kernels honour
-
-
-def _is_hip_tensor(t) -> bool:
-    return t.is_cuda
 
 
 def _f64_route_applies(x, y, xpos, ypos, return_quantiles=False) -> bool:
@@ -334,7 +329,7 @@ class _SortedGridCache:
 _f64_grids = _SortedGridCache()
 
 
-def _f64_row_losses(x, y, xpos, ypos, p, flags):
+def _f64_row_losses(route, x, y, xpos, ypos, p, flags):
     """The float64 route behind Wasserstein1D and wasserstein_1d (_f64_route_applies holds): flat [rows] float64 losses.  The kernels take
     sorted supports, so SOT_FLAG_REQUIRE_SORT is served here: a shared grid is sorted once per tensor version (_SortedGridCache; a grid
     that is sorted already -- the common case -- adds no torch kernel in front of the HIP call), per-row positions per call; the weights
@@ -363,10 +358,7 @@ def _f64_row_losses(x, y, xpos, ypos, p, flags):
             x2, y2 = torch.gather(x2, 1, xi), torch.gather(y2, 1, yi)
         else:
             xp, yp = xp.contiguous(), yp.contiguous()
-    fl = int(flags) & _F64_FLAGS
-    if torch.is_grad_enabled() and (x2.requires_grad or y2.requires_grad):
-        return _RowLossF64.apply(x2, y2, xp, yp, float(p), fl)
-    return nat.forward_rows_f64(x2, y2, xp, yp, float(p), fl)
+    return _flat_rows(route, x2, y2, xp, yp, float(p), int(flags) & _F64_FLAGS, None)   # (the positions are detached: only x2, y2 can ask for a gradient)
 
 
 MIXED_ROUTE = True   # module switch (tests and tools/bench_mixed.py compare both routes): False = mixed supports are materialised as before
@@ -490,15 +482,6 @@ class _Quantiles(torch.autograd.Function):
         return gx, gy, gxp, gyp, None, None, None
 
 
-def _quantile_tensors(x, y, xpos, ypos, p, flags, plan):
-    """return_quantiles on the HIP route: through autograd when a gradient can be asked for, the plain native call otherwise."""
-    if _compiling():
-        return _o.w1d_quantiles(x, y, xpos, ypos, p, flags)
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)):
-        return _Quantiles.apply(x, y, xpos, ypos, p, flags, plan)
-    return nat.quantiles(x, y, xpos, ypos, p, flags, plan)
-
-
 EARLY_GRADIENT = True   # module switch for the loss-and-gradient form below (tests compare both forms)
 
 
@@ -512,12 +495,14 @@ class _FusedMeanLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, xpos, ypos, p, flags, plan):
+        """Shared by _FusedMeanLossBF16: the calls of the rows' element type, looked up on `nat` by name at call time."""
+        typed = "_bf16" if x.dtype is torch.bfloat16 else ""
         ctx.p, ctx.flags, ctx.plan = p, flags, plan
         ctx.early_gy = None
         if ctx.needs_input_grad[1] and not ctx.needs_input_grad[0] and EARLY_GRADIENT:
-            mean, _, ctx.early_gy = nat.loss_and_grad(x, y, xpos, ypos, p, flags, plan)
+            mean, _, ctx.early_gy = getattr(nat, "loss_and_grad" + typed)(x, y, xpos, ypos, p, flags, plan)
         else:
-            mean, _, _ = nat.loss_fused(x, y, xpos, ypos, p, flags, plan)
+            mean = getattr(nat, "loss_fused" + typed)(x, y, xpos, ypos, p, flags, plan)[0]
         ctx.save_for_backward(x, y, xpos, ypos)
         return mean
 
@@ -538,24 +523,13 @@ class _FusedMeanLoss(torch.autograd.Function):
         return gx, gy, gxp, gyp, None, None, None
 
 
-class _FusedMeanLossBF16(torch.autograd.Function):
-    """_FusedMeanLoss for bfloat16 weights where _typed_training_applies holds.  The training step (only y asks for a gradient) is ONE node on
+class _FusedMeanLossBF16(_FusedMeanLoss):
+    """_FusedMeanLoss for bfloat16 weights where _typed_training_applies holds: its forward, a backward of its own.  The training step (only y asks for a gradient) is ONE node on
     16-bit data: its forward is sot_w1d_loss_and_grad_bf16, which stores d mean / d y in bfloat16 before the upstream gradient is known; its
     backward calls the typed backward in fix-up mode on that buffer with the upstream scalar -- an empty launch for a plain loss.backward(),
     a recomputation into the buffer for a weighted loss -- which returns the float32 node's bits rounded once: rne(early gradient * upstream).
     Otherwise (x differentiated, EARLY_GRADIENT off, a second backward through a retained graph): the typed forward + mean, and the typed
     backward with the float32 node's late arguments."""
-
-    @staticmethod
-    def forward(ctx, x, y, xpos, ypos, p, flags, plan):
-        ctx.p, ctx.flags, ctx.plan = p, flags, plan
-        ctx.early_gy = None
-        if ctx.needs_input_grad[1] and not ctx.needs_input_grad[0] and EARLY_GRADIENT:
-            mean, _, ctx.early_gy = nat.loss_and_grad_bf16(x, y, xpos, ypos, p, flags, plan)
-        else:
-            mean, _ = nat.loss_fused_bf16(x, y, xpos, ypos, p, flags, plan)
-        ctx.save_for_backward(x, y, xpos, ypos)
-        return mean
 
     @staticmethod
     def backward(ctx, g):
@@ -611,10 +585,48 @@ class _PlanCache:
         return plan
 
 
-def _prepare(x, y, xpos, ypos, checked=False):
-    """Common marshalling: 2-D fp32 HIP rows and matching positions (checked: the caller has established _hip_domain)."""
-    if not checked:
-        nat.require_hip(x, y, xpos, ypos)
+_functional_plans = _PlanCache()
+
+
+class _Route(typing.NamedTuple):
+    """Where one call goes, decided once by _route() (DESIGN.md section 1.1 has the table)."""
+    family: str                    # "torch": the torch-op composition; "f64": the float64 kernels; "mixed": mixed supports; "rows": the row kernels
+    dtype: torch.dtype             # element type of the weight rows the native call sees (float32 / bfloat16; float64 on "f64")
+    widen: bool = False            # bfloat16 operands are widened first: by _widen on "mixed" / "rows", by .float() on "torch"
+    typed_training: bool = False   # bfloat16 rows that ask for a gradient on the typed training calls (_typed_training_applies)
+
+
+_ROUTE_F64 = _Route("f64", torch.float64)
+
+
+def _route(x, y, xpos, ypos, p, flags, return_quantiles=False) -> _Route:
+    """The gates in their one order, each asked at most once: the float64 gate before _hip_domain can warn, _hip_domain (which refuses half,
+    dtype mixes and bfloat16 positions), _beyond_one_cu, mixed supports, then -- for bfloat16 weights -- the typed forward, the typed
+    training calls, or widening.  Every device test goes through _is_hip_tensor, so meta stand-ins answer too."""
+    if x.dtype is torch.float64 and _f64_route_applies(x, y, xpos, ypos, return_quantiles):
+        return _ROUTE_F64
+    if not _hip_domain(x, y, xpos, ypos):
+        return _Route("torch", x.dtype)
+    bf16 = x.dtype is torch.bfloat16
+    if _beyond_one_cu(x, y, xpos, ypos):
+        return _Route("torch", torch.float32, widen=bf16)   # (rows beyond one CU's LDS: the composition on the upcast weights)
+    mixed = mixed_route_applies(x, y, xpos, ypos, return_quantiles)
+    typed_forward = bf16 and _typed_forward_applies(x, y, xpos, ypos, return_quantiles, mixed)
+    training = bf16 and not typed_forward and _typed_training_applies(x, y, xpos, ypos, return_quantiles, flags, p, mixed)
+    # quantiles, mixed supports, position gradients, rows without 16-bit backward kernels: the float32 path, gradients narrowed
+    widen = bf16 and not typed_forward and not training
+    return _Route("mixed" if mixed else "rows", torch.bfloat16 if bf16 and not widen else torch.float32, widen, training)
+
+
+def _marshal_rows(x, y, xpos, ypos, flags, plans, functional=False):
+    """What the native row calls take: 2-D weight rows, matching positions and the position plan of a shared grid that is to be sorted
+    (traced: the op plans).  The module flattens [batch, time, bins] operands and materialises stride-0 expanded positions per row; the
+    functional form takes 2-D rows only and passes expanded positions (losses.py:167-170) down as one shared row.  Both habits are
+    older than this function and pinned by tests/golden/host_routes.json, so they are kept apart."""
+    if functional:
+        xpos, ypos = [t[0] if (t.ndim == 2 and t.shape[0] > 1 and t.stride(0) == 0) else t for t in (xpos, ypos)]
+    else:
+        x, y, xpos, ypos = [t.reshape(-1, t.shape[-1]) if t.ndim == 3 else t for t in (x, y, xpos, ypos)]
     if x.ndim != 2 or y.ndim != 2:
         raise ValueError(f"expected 2-D [rows, features] weights, got {tuple(x.shape)} and {tuple(y.shape)}")
     if x.shape[0] != y.shape[0]:
@@ -622,21 +634,52 @@ def _prepare(x, y, xpos, ypos, checked=False):
     x, y = nat.rows_view(x), nat.rows_view(y)
     if xpos.shape[-1] != x.shape[1] or ypos.shape[-1] != y.shape[1]:
         raise RuntimeError("positions and weights must have the same number of features")
-    if (xpos.ndim == 1) != (ypos.ndim == 1):  # mixed: materialise the shared row for every batch row
+    if (xpos.ndim == 1) != (ypos.ndim == 1):  # mixed supports outside the mixed route: materialise the shared row for every batch row
         if xpos.ndim == 1:
             xpos = xpos.unsqueeze(0).expand_as(x)
         else:
             ypos = ypos.unsqueeze(0).expand_as(y)
-    if xpos.ndim == 2:
-        if xpos.shape[0] != x.shape[0] or ypos.shape[0] != y.shape[0]:
-            raise RuntimeError("per-row positions must have one row per weight row")
-        xpos, ypos = xpos.contiguous(), ypos.contiguous()
-    else:
-        xpos, ypos = xpos.contiguous(), ypos.contiguous()
-    return x, y, xpos, ypos
+    if xpos.ndim == 2 and (xpos.shape[0] != x.shape[0] or ypos.shape[0] != y.shape[0]):
+        raise RuntimeError("per-row positions must have one row per weight row")
+    xpos, ypos = xpos.contiguous(), ypos.contiguous()
+    plan = plans.get(xpos, ypos) if (flags & nat.FLAG_REQUIRE_SORT and xpos.ndim == 1 and not _compiling()) else None
+    return x, y, xpos, ypos, plan
 
 
-_functional_plans = _PlanCache()
+def _flat_rows(route, x, y, xpos, ypos, p, flags, plan):
+    """The one ladder of the flat row losses, on marshalled rows of the route's element type: the op of a call that is being traced, the
+    autograd node where a gradient can be asked for, the plain native call otherwise."""
+    if _compiling():
+        return (_o.w1d_rows_bf16 if route.dtype is torch.bfloat16 else _o.w1d_rows)(x, y, xpos, ypos, p, flags)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)):
+        return _ROW_NODES[route.dtype].apply(x, y, xpos, ypos, p, flags, plan)
+    return _forward_rows(x, y, xpos, ypos, p, flags, plan)
+
+
+def _native_row_losses(route, x, y, xpos, ypos, p, flags, plans, functional=False):
+    """Flat [rows] losses of a call whose route is not the composition: behind wasserstein_1d, Wasserstein1D.row_losses and the dims /
+    hinge tail of Wasserstein1D.forward."""
+    if route.family == "f64":
+        return _f64_row_losses(route, x, y, xpos, ypos, p, flags)
+    if route.widen:
+        x, y = _widen(x), _widen(y)
+    if route.family == "mixed":   # a shared grid against per-row positions: nothing is materialised
+        return _mixed_row_losses(x, y, xpos, ypos, p, flags, plans)
+    x, y, xpos, ypos, plan = _marshal_rows(x, y, xpos, ypos, flags, plans, functional)
+    return _flat_rows(route, x, y, xpos, ypos, float(p), flags, plan)
+
+
+def _native_quantiles(route, x, y, xpos, ypos, p, flags, plans, functional=False):
+    """return_quantiles on the row kernels (the gates send such a call to no other native family), five [rows, .] tensors: the op of a
+    traced call, through autograd when a gradient can be asked for, the plain native call otherwise."""
+    if route.widen:
+        x, y = _widen(x), _widen(y)
+    x, y, xpos, ypos, plan = _marshal_rows(x, y, xpos, ypos, flags, plans, functional)
+    if _compiling():
+        return _o.w1d_quantiles(x, y, xpos, ypos, float(p), flags)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, xpos, ypos)):
+        return _Quantiles.apply(x, y, xpos, ypos, float(p), flags, plan)
+    return nat.quantiles(x, y, xpos, ypos, float(p), flags, plan)
 
 
 def quantile_function(qs, cws, xs):
@@ -656,34 +699,16 @@ def wasserstein_1d(u_values, v_values, u_weights=None, v_weights=None, p=1, requ
         u_weights = torch.full(u_values.shape, 1.0 / n, device=u_values.device, dtype=u_values.dtype)
     if v_weights is None:
         v_weights = torch.full(v_values.shape, 1.0 / m, device=v_values.device, dtype=v_values.dtype)
-    if u_weights.dtype is torch.float64 and _f64_route_applies(u_weights, v_weights, u_values, v_values, return_quantiles):
-        return _f64_row_losses(u_weights, v_weights, u_values, v_values, p, _flags(False, False, limit_quantile_range, require_sort, prenormalized=True))
-    if not _hip_domain(u_weights, v_weights, u_values, v_values) or _beyond_one_cu(u_weights, v_weights, u_values, v_values):
-        if u_weights.is_cuda and u_weights.dtype is torch.bfloat16:   # (rows beyond one CU's LDS: the composition on the upcast weights)
+    flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
+    route = _route(u_weights, v_weights, u_values, v_values, p, flags, return_quantiles)
+    if route.family == "torch":
+        if route.widen:
             u_weights, v_weights = u_weights.float(), v_weights.float()
         return tp.transport_rows(u_values, v_values, u_weights, v_weights, p=p, require_sort=require_sort,
                                  return_quantiles=return_quantiles, limit_quantile_range=limit_quantile_range)
-    if u_weights.dtype is torch.bfloat16 and not _typed_forward_applies(u_weights, v_weights, u_values, v_values, return_quantiles):
-        u_weights, v_weights = _widen(u_weights), _widen(v_weights)
-
-    if mixed_route_applies(u_weights, v_weights, u_values, v_values, return_quantiles):
-        flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
-        return _mixed_row_losses(u_weights, v_weights, u_values, v_values, p, flags, _functional_plans)
-
-    # stride-0 expanded positions (losses.py:167-170) are passed down as one shared row
-    def shared_row(t):
-        return t[0] if (t.ndim == 2 and t.shape[0] > 1 and t.stride(0) == 0) else t
-    upos, vpos = shared_row(u_values), shared_row(v_values)
-    x, y, upos, vpos = _prepare(u_weights, v_weights, upos, vpos, checked=True)   # (_hip_domain above)
-    flags = _flags(False, False, limit_quantile_range, require_sort, prenormalized=True)
-    plan = _functional_plans.get(upos, vpos) if (require_sort and upos.ndim == 1 and not _compiling()) else None
     if return_quantiles:
-        return _quantile_tensors(x, y, upos, vpos, float(p), flags, plan)
-    if x.dtype is torch.bfloat16:   # no gradient asked for: the typed forward
-        return _o.w1d_rows_bf16(x, y, upos, vpos, float(p), flags) if _compiling() else nat.forward_rows_bf16(x, y, upos, vpos, float(p), flags, plan)
-    if _compiling():
-        return _o.w1d_rows(x, y, upos, vpos, float(p), flags)
-    return _RowLoss.apply(x, y, upos, vpos, float(p), flags, plan)
+        return _native_quantiles(route, u_weights, v_weights, u_values, v_values, p, flags, _functional_plans, functional=True)
+    return _native_row_losses(route, u_weights, v_weights, u_values, v_values, p, flags, _functional_plans, functional=True)
 
 
 def _csr_to_padded(weights, positions, offsets, width):
@@ -807,26 +832,15 @@ class Wasserstein1D(torch.nn.Module):
         return flags
 
     def _marshal(self, x, y, x_pos, y_pos, kwargs):
-        """float32 GPU tensors -> what the native calls take: 2-D rows, positions, flag word, position plan."""
+        """HIP-domain tensors -> what the native calls take: 2-D rows, positions, flag word, position plan (and the leading shape)."""
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
-        original_shape = x.shape[:-1]
-        if x.ndim == 3:
-            x = x.reshape(-1, x.shape[-1])
-        if y.ndim == 3:
-            y = y.reshape(-1, y.shape[-1])
-        if x_pos_.ndim == 3:
-            x_pos_ = x_pos_.reshape(-1, x_pos_.shape[-1])
-        if y_pos_.ndim == 3:
-            y_pos_ = y_pos_.reshape(-1, y_pos_.shape[-1])
-
         flags = self._flag_word(kwargs)
-        x, y, x_pos_, y_pos_ = _prepare(x, y, x_pos_, y_pos_, checked=True)
-        plan = self._plans.get(x_pos_, y_pos_) if (self.require_sort and x_pos_.ndim == 1 and not _compiling()) else None   # traced: the op plans
-        return x, y, x_pos_, y_pos_, flags, plan, original_shape
+        x2, y2, x_pos_, y_pos_, plan = _marshal_rows(x, y, x_pos_, y_pos_, flags, self._plans)
+        return x2, y2, x_pos_, y_pos_, flags, plan, x.shape[:-1]
 
-    def _torch_forward(self, x, y, x_pos_, y_pos_, kwargs, rows_only=False):
+    def _torch_forward(self, route, x, y, x_pos_, y_pos_, kwargs, rows_only=False):
         """CPU / float64 tensors: the torch-op composition (_torch_path.py), same keyword handling as the HIP route."""
-        if x.is_cuda and x.dtype is torch.bfloat16 and y.dtype is torch.bfloat16:   # (rows beyond one CU's LDS: on the upcast weights)
+        if route.widen:   # (bfloat16 rows beyond one CU's LDS: on the upcast weights)
             x, y = x.float(), y.float()
         return tp.module_forward(
             x, y, x_pos_, y_pos_, p=self.p, square_dist=self.square_dist,
@@ -836,9 +850,11 @@ class Wasserstein1D(torch.nn.Module):
             dims=(0 if rows_only else kwargs.get("dims", None)), return_quantiles=(not rows_only) and kwargs.get("return_quantiles", False),
             rows_only=rows_only)
 
-    def _f64_rows(self, x, y, x_pos_, y_pos_, kwargs):
-        """float64 GPU tensors on the float64 kernels (_f64_route_applies holds): the flat row losses after the optional hinge."""
-        loss = _f64_row_losses(x, y, x_pos_, y_pos_, self.p, self._flag_word(kwargs))
+    def _rows(self, route, x, y, x_pos_, y_pos_, flags, kwargs):
+        """The flat row losses of a routed call after the optional hinge."""
+        if route.family == "torch":
+            return self._torch_forward(route, x, y, x_pos_, y_pos_, kwargs, rows_only=True)
+        loss = _native_row_losses(route, x, y, x_pos_, y_pos_, self.p, flags, self._plans)
         if self.hinge:
             loss = torch.nn.functional.relu(loss - kwargs.get("hinge", 0.0))
         return loss
@@ -847,31 +863,41 @@ class Wasserstein1D(torch.nn.Module):
         """Flat [rows] tensor of W_p^p per spectrum pair (after the optional hinge, before the mean):
         what losses.py:186-205 holds before its reshape/mean.  Used by the row-sharded multi-GPU path."""
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
-        if x.dtype is torch.float64 and _f64_route_applies(x, y, x_pos_, y_pos_):
-            return self._f64_rows(x, y, x_pos_, y_pos_, kwargs)
-        if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
-            return self._torch_forward(x, y, x_pos_, y_pos_, kwargs, rows_only=True)
-        if x.dtype is torch.bfloat16 and not (_typed_forward_applies(x, y, x_pos_, y_pos_)
-                                              or _typed_training_applies(x, y, x_pos_, y_pos_, False, self._flag_word(kwargs), self.p)):
+        flags = self._flag_word(kwargs)
+        return self._rows(_route(x, y, x_pos_, y_pos_, self.p, flags), x, y, x_pos_, y_pos_, flags, kwargs)
+
+    def _fused_mean(self, route, x, y, x_pos_, y_pos_, flags, fresh_grids, kwargs):
+        """Default reduction on the row kernels: forward and the mean over every row (losses.py:211) in one native call.  fresh_grids: both
+        position tensors came with the call (not the fixed_x buffer)."""
+        if route.widen:
             x, y = _widen(x), _widen(y)
-        if mixed_route_applies(x, y, x_pos_, y_pos_):   # a shared grid against per-row positions: nothing is materialised
-            loss = _mixed_row_losses(x, y, x_pos_, y_pos_, self.p, self._flag_word(kwargs), self._plans)
-        else:
-            x, y, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
-            if x.dtype is torch.bfloat16 and not _compiling() and torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
-                loss = _RowLossBF16.apply(x, y, x_pos_, y_pos_, float(self.p), flags, plan)   # (_typed_training_applies held)
-            elif x.dtype is torch.bfloat16:   # no gradient asked for: the typed forward
-                loss = (_o.w1d_rows_bf16(x, y, x_pos_, y_pos_, float(self.p), flags) if _compiling()
-                        else nat.forward_rows_bf16(x, y, x_pos_, y_pos_, float(self.p), flags, plan))
-            elif _compiling():
-                loss = _o.w1d_rows(x, y, x_pos_, y_pos_, float(self.p), flags)
-            elif torch.is_grad_enabled() and any(t.requires_grad for t in (x, y, x_pos_, y_pos_)):
-                loss = _RowLoss.apply(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
-            else:
-                loss = nat.forward_rows(x, y, x_pos_, y_pos_, float(self.p), flags, plan)
-        if self.hinge:
-            loss = torch.nn.functional.relu(loss - kwargs.get("hinge", 0.0))
-        return loss
+        x2, y2, x_pos_, y_pos_, plan = _marshal_rows(x, y, x_pos_, y_pos_, flags, self._plans)
+        p, typed = float(self.p), route.dtype is torch.bfloat16   # typed: _typed_training_applies held, or no gradient is asked for
+        grad_on = torch.is_grad_enabled()
+        if _compiling():   # the native calls below, as ops: the training form when only y (and positions) ask for a gradient
+            if typed:
+                return _o.w1d_mean_bf16(x2, y2, x_pos_, y_pos_, p, flags)
+            if grad_on and EARLY_GRADIENT and y2.requires_grad and not x2.requires_grad:
+                return _o.w1d_mean_and_grad(x2, y2, x_pos_, y_pos_, p, flags)[0]
+            return _o.w1d_mean(x2, y2, x_pos_, y_pos_, p, flags)
+        glue = nat.glue() if (plan is not None and EARLY_GRADIENT and not typed) else None
+        if glue is not None and not (grad_on and (x2.requires_grad or x_pos_.requires_grad or y_pos_.requires_grad)):
+            # the hot call (trainer.py:220-228: gradient for the estimate's spectrum only; metrics.py:148: none): C++ host path
+            plan.use_on_current_stream(x2.device)
+            fl = nat.problem_flags(self.p, flags, plan)
+            # remember the hot call (see forward) -- not from inside a stream capture, where plan.same_grid() answers "no" without
+            # remembering it and the flag word frozen here would lack SOT_FLAG_SAME_GRID for good
+            if (not kwargs and x_pos_.ndim == 1 and y_pos_.ndim == 1 and x2.shape[1] + y2.shape[1] <= 12000
+                    and not torch.cuda.is_current_stream_capturing()):
+                self._hot = _HotCall(
+                    x_pos=x_pos_, y_pos=y_pos_, x_version=_version_of(x_pos_), y_version=_version_of(y_pos_), settings=self._settings(), plan=plan,
+                    flag_word=fl, glue=glue, n=x2.shape[1], m=y2.shape[1],
+                    fresh_ok=fresh_grids and hasattr(glue, "mean_loss_fresh"), flags_no_same_grid=int(flags),
+                    area_ok=self.p == 1 and not (flags & (nat.FLAG_LIMIT_Q | nat.FLAG_NO_AREA | nat.FLAG_PRENORMALIZED)))
+            return glue.mean_loss(x2, y2, plan.xpos_sorted, plan.ypos_sorted, plan.xperm, plan.yperm, plan.ident, p, fl)
+        if grad_on and any(t.requires_grad for t in (x2, y2, x_pos_, y_pos_)):
+            return (_FusedMeanLossBF16 if route.typed_training else _FusedMeanLoss).apply(x2, y2, x_pos_, y_pos_, p, flags, plan)
+        return getattr(nat, "loss_fused_bf16" if typed else "loss_fused")(x2, y2, x_pos_, y_pos_, p, flags, plan)[0]
 
     def _settings(self):
         return (self.p, self.square_dist, self.dont_normalize, self.limit_quantile_range, self.require_sort, self.hinge,
@@ -910,64 +936,21 @@ class Wasserstein1D(torch.nn.Module):
                         and not (torch.is_grad_enabled() and (x2.requires_grad or xp.requires_grad or yp.requires_grad))):
                     return hot.glue.mean_loss_fresh(x2, y2, xp, yp, float(self.p), hot.flags_no_same_grid | (nat.FLAG_SAME_GRID if (xp is yp and hot.area_ok) else 0))
         x_pos_, y_pos_ = self._positions(x_pos, y_pos)
-        if x.dtype is torch.float64 and _f64_route_applies(x, y, x_pos_, y_pos_, kwargs.get("return_quantiles", False)):
-            # the float64 kernels; hinge, dims and the mean stay torch ops on the float64 row losses (losses.py:203-211)
-            loss = self._f64_rows(x, y, x_pos_, y_pos_, kwargs)
-            return torch.mean(loss.reshape(x.shape[:-1]), dim=kwargs.get("dims", None))
-        if not _hip_domain(x, y, x_pos_, y_pos_) or _beyond_one_cu(x, y, x_pos_, y_pos_):
-            return self._torch_forward(x, y, x_pos_, y_pos_, kwargs)
-        if x.dtype is torch.bfloat16:
-            rq = kwargs.get("return_quantiles", False)
-            if not (_typed_forward_applies(x, y, x_pos_, y_pos_, rq) or _typed_training_applies(x, y, x_pos_, y_pos_, rq, self._flag_word(kwargs), self.p)):
-                x, y = _widen(x), _widen(y)   # quantiles, mixed supports, position gradients, rows without 16-bit backward kernels: the float32 path, gradients narrowed
-        return self._hip_forward(x, y, x_pos, y_pos, x_pos_, y_pos_, kwargs)
-
-    def _hip_forward(self, x, y, x_pos, y_pos, x_pos_, y_pos_, kwargs):
-        if kwargs.get("return_quantiles", False):
-            x2, y2, x_pos_, y_pos_, flags, plan, original_shape = self._marshal(x, y, x_pos, y_pos, kwargs)
-            out = _quantile_tensors(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)
-            return [t.reshape(original_shape + (-1,)) for t in out]
-
-        original_shape = x.shape[:-1]
+        flags = self._flag_word(kwargs)
+        quantiles = kwargs.get("return_quantiles", False)
+        route = _route(x, y, x_pos_, y_pos_, self.p, flags, quantiles)
+        if route.family == "torch":
+            return self._torch_forward(route, x, y, x_pos_, y_pos_, kwargs)
+        if quantiles:
+            out = _native_quantiles(route, x, y, x_pos_, y_pos_, self.p, flags, self._plans)
+            return [t.reshape(x.shape[:-1] + (-1,)) for t in out]
         dims = kwargs.get("dims", None)
-        if dims is None and not self.hinge and not mixed_route_applies(x, y, x_pos_, y_pos_):
-            # default reduction: forward and the mean over every row (losses.py:211) in one native call
-            x2, y2, x_pos_, y_pos_, flags, plan, _ = self._marshal(x, y, x_pos, y_pos, kwargs)
-            grad_on = torch.is_grad_enabled()
-            if x2.dtype is torch.bfloat16:   # a gradient w.r.t. the weights on the typed route (_typed_training_applies held), or none asked for
-                if _compiling():
-                    return _o.w1d_mean_bf16(x2, y2, x_pos_, y_pos_, float(self.p), flags)
-                if grad_on and (x2.requires_grad or y2.requires_grad):
-                    return _FusedMeanLossBF16.apply(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)
-                # the typed forward + batch mean, one native call
-                return nat.loss_fused_bf16(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)[0]
-            if _compiling():   # the same two native calls as below, as ops: the training form when only y (and positions) ask for a gradient
-                if grad_on and EARLY_GRADIENT and y2.requires_grad and not x2.requires_grad:
-                    return _o.w1d_mean_and_grad(x2, y2, x_pos_, y_pos_, float(self.p), flags)[0]
-                return _o.w1d_mean(x2, y2, x_pos_, y_pos_, float(self.p), flags)
-            glue = nat.glue() if (plan is not None and EARLY_GRADIENT) else None
-            if glue is not None and not (grad_on and (x2.requires_grad or x_pos_.requires_grad or y_pos_.requires_grad)):
-                # the hot call (trainer.py:220-228: gradient for the estimate's spectrum only; metrics.py:148: none): C++ host path
-                plan.use_on_current_stream(x2.device)
-                fl = nat.problem_flags(self.p, flags, plan)
-                # remember the hot call (see forward) -- not from inside a stream capture, where plan.same_grid() answers "no" without
-                # remembering it and the flag word frozen here would lack SOT_FLAG_SAME_GRID for good
-                if (not kwargs and x_pos_.ndim == 1 and y_pos_.ndim == 1 and x2.shape[1] + y2.shape[1] <= 12000
-                        and not torch.cuda.is_current_stream_capturing()):
-                    self._hot = _HotCall(
-                        x_pos=x_pos_, y_pos=y_pos_, x_version=_version_of(x_pos_), y_version=_version_of(y_pos_), settings=self._settings(), plan=plan,
-                        flag_word=fl, glue=glue, n=x2.shape[1], m=y2.shape[1],
-                        fresh_ok=x_pos is not None and y_pos is not None and hasattr(glue, "mean_loss_fresh"), flags_no_same_grid=int(flags),
-                        area_ok=self.p == 1 and not (flags & (nat.FLAG_LIMIT_Q | nat.FLAG_NO_AREA | nat.FLAG_PRENORMALIZED)))
-                return glue.mean_loss(x2, y2, plan.xpos_sorted, plan.ypos_sorted, plan.xperm, plan.yperm, plan.ident, float(self.p), fl)
-            if grad_on and any(t.requires_grad for t in (x2, y2, x_pos_, y_pos_)):
-                return _FusedMeanLoss.apply(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)
-            return nat.loss_fused(x2, y2, x_pos_, y_pos_, float(self.p), flags, plan)[0]
-        loss = self.row_losses(x, y, x_pos, y_pos, **kwargs)
-        if dims is None:
+        if route.family == "rows" and dims is None and not self.hinge:
+            return self._fused_mean(route, x, y, x_pos_, y_pos_, flags, x_pos is not None and y_pos is not None, kwargs)
+        loss = self._rows(route, x, y, x_pos_, y_pos_, flags, kwargs)
+        if dims is None and route.family != "f64":   # (float64 row losses: the mean stays a torch op, losses.py:203-211)
             return _o.row_mean(loss) if _compiling() else _RowMean.apply(loss)  # torch.mean over every row -> 0-d tensor (losses.py:211)
-        loss = loss.reshape(original_shape)
-        return torch.mean(loss, dim=dims)
+        return torch.mean(loss.reshape(x.shape[:-1]), dim=dims)
 
 
 class _MultiScaleSpectral(torch.autograd.Function):
